@@ -3,10 +3,10 @@
 
 A "step" is one ``LangevinDynamics.sample()`` call over the per-GPU batch of BASELINE
 config 2: DoubleWell(h=2, b=1), n_chains = 2^20, dim = 64, k = 200 Euler-Maruyama steps,
-eta = 0.01, sigma = 1, fp32, initial state already resident in HBM.  One call = one launch
+eta = 0.01, sigma = 1, fp32, initial state N(0, 1) clamped to [-4, 4] and already resident in HBM.  One call = one launch
 of the fused kernel ``ebm_langevin_chain_f32`` = n_chains * k chain-steps.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 ``--gpus N`` with N > 1 and no torchrun environment (``WORLD_SIZE`` unset) launches the N ranks
@@ -14,6 +14,8 @@ ITSELF: the process re-executes this file under ``torch.distributed.run`` (127.0
 free port) and relays rank 0's JSON line; it fails loudly when fewer than N GPUs are visible.
 
 The K timed steps continue the same chains (each call starts from the previous call's state).
+``--dump-outputs DIR`` writes the final state of the K-th step (a fixed, seeded row sample of it) as .npy files; the
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 N > 1: one process per GPU, chains sharded by rank (weak scaling: 2^20 chains per GPU, seed
 base+rank, no collective inside the k steps).  The only exchange on the path is the read-back
@@ -79,8 +81,14 @@ def parse():
     ap.add_argument("--no-extra", action="store_true", help="skip the other BASELINE configs (the `extra` array)")
     ap.add_argument("--no-traffic", action="store_true", help="do not re-run two launches under rocprofv3 --pmc for roofline.traffic "
                                                               "(the committed profiles/traffic.json is used instead)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)  # the process rocprofv3 wraps: three launches, no output
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
     # --config 4 = BASELINE configs[3]'s per-GPU shard: args.n_chains, args.dim, args.k = 1 << 20, 128, 500 unless given explicitly
     # (a reduced shard lets the 8-rank code path run on CPU ranks: tests/test_distributed.py)
     preset = (1 << 20, 128, 500) if args.config == 4 else (1 << 20, 64, 200)
@@ -88,6 +96,25 @@ def parse():
     args.dim = preset[1] if args.dim is None else args.dim
     args.k = preset[2] if args.k is None else args.k
     return args
+
+
+DUMP_BYTES = 32 << 20  # the final state is sampled down to at most this many bytes
+
+
+def dump_outputs(out_dir, final):
+    """Write what the last timed step returned to the caller -- the final [n, dim] chain state (the all-gathered
+    state with N > 1) -- as float32 .npy files.  A state larger than DUMP_BYTES is sampled by rows: a fixed,
+    seeded, sorted subset whose indices go to ``rows.npy`` (float64, exact), so two builds run with the same
+    arguments can be compared element for element."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    n, width = final.shape[0], final[0].numel()
+    keep = min(n, max(1, DUMP_BYTES // (4 * width)))
+    rows = torch.arange(n) if keep == n else torch.randperm(n, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+    picked = final.index_select(0, rows.to(final.device)).detach().to("cpu", torch.float32).contiguous()
+    np.save(os.path.join(out_dir, "final_state.npy"), picked.numpy())
+    np.save(os.path.join(out_dir, "rows.npy"), rows.to(torch.float64).numpy())
 
 
 # ---------------------------------------------------------------------------------------
@@ -904,7 +931,9 @@ def main():
     model = ta.DoubleWellModel(barrier_height=2.0, b=1.0, device=device)
     sampler = ta.LangevinDynamics(model, step_size=ETA, noise_scale=SIGMA, device=device)
     gen = torch.Generator(device=device).manual_seed(1234 + rank)
-    x0 = torch.randn(n, dim, device=device, generator=gen)
+    # Clamped to [-4, 4] like smoke()'s start states: at eta = 0.01 the DoubleWell drift throws a coordinate that starts beyond
+    # |x| ~ 5.1 across the well ever further until it overflows, and a normal draw of 2^26 has a few dozen such coordinates.
+    x0 = torch.randn(n, dim, device=device, generator=gen).clamp_(-4.0, 4.0)
 
     gathered = None
     pieces = 4 if n % 4 == 0 else 1
@@ -956,6 +985,9 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     elapsed_local = elapsed
+    final = None
+    if args.dump_outputs and rank == 0:  # what the last timed step returned, copied before anything below samples again
+        final = (state if gathered is None else gathered.reshape(world * n, *state.shape[1:])).clone()
     timed_pairs = _lib.timed_events.pop("ebm_langevin_chain_f32") if on_gpu else []  # the K timed steps' launches only
 
     if world > 1:
@@ -1152,6 +1184,8 @@ def main():
                                                (roof or {}).get("valu", {}).get("issue_units_per_float4_group_step") or LEAN_LOOP_ISSUE_UNITS,
                                                cpu=not args.no_cpu_baseline,
                                                mixed_s_per_wave_trip=((roof or {}).get("valu", {}).get("issue_costs_measured_in_run") or {}).get("mixed_stream_s_per_wave_trip"))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, final)
         print(json.dumps(line), flush=True)
 
     if world > 1:

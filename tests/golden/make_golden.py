@@ -291,6 +291,10 @@ def main():
     # ---- Energy Matching negatives ---------------------------------
     energy_matching_cases()
 
+    # ---- contrastive divergence and the dataset generators -----------------------------
+    cd_case()
+    datasets_case()
+
 
 def hmc_wide_gaussian_cases():
     """Correlated Gaussians at the dims the matrix-core HMC kernel covers (32, 64), no mass / scalar mass."""
@@ -387,6 +391,32 @@ def hmc_survey():
           "ref": {"x": x, "sha_x": sha(x), "acceptance_rate": d["acceptance_rate"]}}
     torch.save(fx, os.path.join(HERE, "survey_hmc_dw.pt"))
     print(f"survey_hmc_dw                x sha {sha(x)} (SURVEY: d807b174f55c084b)")
+
+
+def cd_case():
+    """The reference's ContrastiveDivergence(k_steps=5) driving its own LangevinDynamics on DoubleWell: loss and negatives."""
+    from torchebm.losses import ContrastiveDivergence
+
+    x = torch.randn(64, 4, generator=torch.Generator().manual_seed(0))
+    model = DoubleWellModel()
+    loss, neg = ContrastiveDivergence(model, LangevinDynamics(model, step_size=0.01), k_steps=5)(
+        x, generator=torch.Generator().manual_seed(1))
+    fx = {"name": "cd_dw_64x4", "x": x, "k": 5, "step_size": 0.01, "seed": 1,
+          "ref": {"loss": loss.detach(), "negatives": neg, "sha_negatives": sha(neg)}}
+    torch.save(fx, os.path.join(HERE, "cd_dw_64x4.pt"))
+    print(f"cd_dw_64x4                   negatives sha {sha(neg)}  loss {loss.item():+.6f}")
+
+
+def datasets_case():
+    """The reference's two-moons and ring-mixture generators at the seeds tests/test_host_api.py checks."""
+    from torchebm.datasets import GaussianMixtureDataset, TwoMoonsDataset
+
+    fx = {"name": "datasets", "moons": {}, "ring": {}}
+    for seed in (0, 4):
+        fx["moons"][seed] = TwoMoonsDataset(301, 0.05, seed=seed).get_data()
+        fx["ring"][seed] = GaussianMixtureDataset(2001, 8, 0.05, 4.0, seed=seed).get_data()
+    torch.save(fx, os.path.join(HERE, "datasets.pt"))
+    print("datasets                     moons " + " ".join(sha(t) for t in fx["moons"].values()))
 
 
 if __name__ == "__main__":

@@ -482,34 +482,15 @@ def test_pcd_training_step_with_real_sampler_cpu():
     assert any(not torch.equal(a, b) for a, b in zip(before, model.parameters()))
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/torchebm"), reason="reference checkout not present")
-def test_reference_cd_runs_unmodified_on_this_sampler():
-    """Drop-in check (authoring container only): the REFERENCE's ContrastiveDivergence drives this
-    package's LangevinDynamics and gets the same negatives as with its own sampler."""
-    import subprocess
-    import sys
-
-    code = r'''
-import sys, types
-sys.dont_write_bytecode = True
-sys.path.insert(0, "/root/reference"); sys.path.insert(0, %r)
-v = types.ModuleType("torchebm._version"); v.__version__ = "0"; sys.modules["torchebm._version"] = v
-import torch
-from torchebm.core import DoubleWellModel as RefDW
-from torchebm.losses import ContrastiveDivergence as RefCD
-from torchebm.samplers import LangevinDynamics as RefLD
-import torchebm_amd as ta
-x = torch.randn(64, 4, generator=torch.Generator().manual_seed(0))
-ref_model = RefDW()
-mine = ta.LangevinDynamics(ta.DoubleWellModel(), step_size=0.01)
-theirs = RefLD(ref_model, step_size=0.01)
-la, na = RefCD(ref_model, mine, k_steps=5)(x, generator=torch.Generator().manual_seed(1))
-lb, nb = RefCD(ref_model, theirs, k_steps=5)(x, generator=torch.Generator().manual_seed(1))
-assert torch.equal(na, nb) and torch.equal(la, lb)
-print("dropin-ok")
-''' % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert "dropin-ok" in out.stdout, out.stderr[-2000:]
+def test_cd_reproduces_reference_loss_and_negatives():
+    """ContrastiveDivergence(k_steps=5) over this package's LangevinDynamics gets the loss and the negatives the reference's
+    ContrastiveDivergence got over its own sampler from the same seeds (recorded in tests/golden/cd_dw_64x4.pt)."""
+    fx = load_golden("cd_dw_64x4")
+    model = ta.DoubleWellModel()
+    sampler = ta.LangevinDynamics(model, step_size=fx["step_size"])
+    loss, neg = ta.ContrastiveDivergence(model, sampler, k_steps=fx["k"])(fx["x"], generator=torch.Generator().manual_seed(fx["seed"]))
+    assert torch.equal(neg, fx["ref"]["negatives"])
+    assert torch.equal(loss.detach(), fx["ref"]["loss"])
 
 
 @pytest.mark.parametrize("name", golden_names("heun_"))
@@ -611,7 +592,7 @@ def test_three_d_state_of_an_analytic_energy_raises_like_the_reference():
 
 def test_datasets_module():
     """torchebm_amd.datasets: the two generators on the path (two-moons = config 5's data, the ring mixture = config 3's
-    centres); equal to the reference's tensors for the same seed where the reference is present."""
+    centres); equal to the reference's tensors for the same seed (tests/golden/datasets.pt)."""
     from torchebm_amd.datasets import GaussianMixtureDataset, TwoMoonsDataset
 
     moons = TwoMoonsDataset(n_samples=301, noise=0.05, seed=3)
@@ -637,25 +618,10 @@ def test_datasets_module():
     assert torch.bincount(nearest, minlength=8).tolist() == [251] + [250] * 7
     with pytest.raises(ValueError):
         GaussianMixtureDataset(n_components=0)
-    if os.path.isdir("/root/reference/torchebm"):  # authoring container: the reference's own generators, same seeds
-        import subprocess
-        import sys
-
-        code = r'''
-import sys, types
-sys.dont_write_bytecode = True
-sys.path.insert(0, "/root/reference"); sys.path.insert(0, %r)
-v = types.ModuleType("torchebm._version"); v.__version__ = "0"; sys.modules["torchebm._version"] = v
-import torch
-from torchebm.datasets import TwoMoonsDataset as RefMoons, GaussianMixtureDataset as RefRing
-from torchebm_amd.datasets import TwoMoonsDataset, GaussianMixtureDataset
-for seed in (0, 4):
-    assert torch.equal(TwoMoonsDataset(301, 0.05, seed=seed).get_data(), RefMoons(301, 0.05, seed=seed).get_data())
-    assert torch.equal(GaussianMixtureDataset(2001, 8, 0.05, 4.0, seed=seed).get_data(), RefRing(2001, 8, 0.05, 4.0, seed=seed).get_data())
-print("datasets-ok")
-''' % os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-        out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-        assert "datasets-ok" in out.stdout, out.stderr[-2000:]
+    ref = load_golden("datasets")  # the reference's own generators, same seeds
+    for seed in (0, 4):
+        assert torch.equal(TwoMoonsDataset(301, 0.05, seed=seed).get_data(), ref["moons"][seed])
+        assert torch.equal(GaussianMixtureDataset(2001, 8, 0.05, 4.0, seed=seed).get_data(), ref["ring"][seed])
 
 
 def test_descriptor_keeps_its_tensors_alive():
