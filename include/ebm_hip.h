@@ -314,7 +314,8 @@ EBM_API int ebm_pcd_scatter_f32(float* buffer, int64_t buffer_size, int32_t dim,
  * ebm_langevin_step_dev_f32 / ebm_noise_fill_dev_f32: rng_state = {seed, step}; the launch draws at step rng_state[1] + step_delta.
  *   ebm_langevin_chain_dev_f32: ebm_langevin_chain_f32 with native draws (no injected noise, no diagnostics records) at steps
  *       rng_state[1] + step_delta .. + k_steps - 1.  Energies: EBM_ENERGY_MLP (every shape the chain kernel takes); EBM_EKIND
- *       for the others (their kernels take the coordinates by value).
+ *       for the others (their kernels take the coordinates by value).  `clamp_on` is the same flag word: unknown bits are
+ *       EBM_EINVAL, and EBM_CHAIN_CONTRACTED is accepted and ignored (the MLP kernels never contract).
  *   ebm_pcd_gather_dev_f32: ebm_pcd_gather_f32 with native offsets drawn at step rng_state[1] + step_delta.
  *   ebm_pcd_scatter_dev_f32: ebm_pcd_scatter_f32 with the write position read from *write_pos (device int64, 0 <= *write_pos
  *       < buffer_size; advancing it is the caller's: (pos + batch) % buffer_size).

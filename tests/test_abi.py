@@ -56,6 +56,10 @@ def test_argument_errors_do_not_need_a_gpu():
         _lib.call("ebm_langevin_chain_f32", desc, 16, 8, 4, 3, 0.1, 0.3, 1.0, None, 0, 0.0, 0.0, 1, None, None, None, 0, 0, None)
     with pytest.raises(ValueError, match="16-byte aligned"):
         _lib.call("ebm_noise_fill_f32", 4, 8, 0, 0, 0, None)
+    # the device-RNG chain decodes the same flag word, before its early return for an empty call
+    desc.kind, desc.dev0 = _lib.ENERGY_MLP, 16
+    with pytest.raises(ValueError, match="unknown bits"):
+        _lib.call("ebm_langevin_chain_dev_f32", desc, 16, 0, 4, 3, 0.1, 0.3, 1.0, None, 4, 0.0, 0.0, 1, None, 16, 0, None)
 
 
 @pytest.mark.gpu

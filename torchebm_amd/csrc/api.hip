@@ -5,38 +5,17 @@
 #include <cstdio>
 #include <cstdlib>
 
-#include "diag.h"
-#include "ebm_common.h"
+#include "chain_launch.h"
 
 namespace ebm {
 
-// launchers implemented in the kernel translation units
+// launchers implemented in the kernel translation units (the chain launchers: chain_launch.h)
 int launch_langevin_step(const float*, const float*, float*, const float*, int64_t, float, float,
                          float, int, float, float, uint64_t, uint64_t, const uint64_t*, hipStream_t);
 int launch_langevin_step_diffusion(const float*, const float*, float*, const float*, const float*, int64_t, int64_t, float, float,
                                    uint64_t, uint64_t, hipStream_t);
-int launch_langevin_chain_elem(int, float, float, float*, int64_t, int32_t, int32_t, float, float,
-                               float, const float*, int, float, float, int32_t, float*,
-                               const float*, uint64_t, uint64_t, int heun, int contracted, hipStream_t);
-int launch_langevin_chain_rows(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, float, float,
-                               float, const float*, int, float, float, int32_t, float*,
-                               const float*, uint64_t, uint64_t, int heun, float* diag_partials, hipStream_t);
-int launch_langevin_chain_elem_diag(int, float, float, float*, int64_t, int32_t, int32_t, float, float, float,
-                                    const float*, int, float, float, int32_t, float*, uint64_t, uint64_t, int heun,
-                                    float* diag_partials, hipStream_t);
-bool elem_diag_supported(int32_t dim, bool has_noise, bool has_traj);
-bool elem_diag_plan(int64_t n_chains, int32_t dim, diag::DiagArgs&);
-bool rows_langevin_diag_plan(const ebm_energy_t&, int heun, int64_t n_chains, int32_t dim, diag::DiagArgs&);
-bool hmc_diag_plan(const ebm_energy_t&, int64_t n_chains, int32_t dim, diag::DiagArgs&);
 int launch_diag_finish(const float*, int32_t, int64_t, int32_t, int32_t, int64_t, int32_t, float*, float*, float*, float*,
                        double*, hipStream_t);
-int launch_hmc_chain_mlp(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, int32_t, float, const float*, int32_t,
-                         double, const float*, int32_t, float*, uint8_t*, uint32_t*, const float*, const float*,
-                         uint64_t, uint64_t, float*, hipStream_t);
-bool mlp_diag_plan(const ebm_energy_t&, bool hmc, int64_t, int32_t, diag::DiagArgs&);  // mlp.hip
-int launch_hmc_chain(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, int32_t, float,
-                     const float*, int32_t, double, const float*, int32_t, float*, uint8_t*,
-                     uint32_t*, const float*, const float*, uint64_t, uint64_t, float* diag_partials, hipStream_t);
 int launch_leapfrog_kick_drift(const float*, const float*, const float*, float*, float*, int64_t,
                                int32_t, float, int32_t, double, const float*, int32_t, hipStream_t);
 int launch_leapfrog_kick(float*, const float*, const float*, float*, int64_t, float, int32_t,
@@ -51,8 +30,6 @@ int launch_descent_chain(const ebm_energy_t&, float*, int64_t, int32_t, int32_t,
 int launch_descent_step(const float*, const float*, float*, float*, int64_t, float, float, hipStream_t);
 int launch_lookahead(const float*, const float*, float*, int64_t, float, hipStream_t);
 int launch_gmm_active_columns(const float*, int32_t, int32_t, int32_t*, hipStream_t);
-int launch_hmc_chain_audit(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, int32_t, float, const float*, int32_t, double,
-                           const float*, int32_t, float*, uint8_t*, uint32_t*, const float*, const float*, uint64_t, uint64_t, hipStream_t);
 int launch_pcd_gather(const float*, int64_t, int32_t, float*, int64_t, int64_t, const int64_t*, int64_t*, uint64_t,
                       uint64_t, const uint64_t*, hipStream_t);
 int launch_pcd_scatter(float*, int64_t, int32_t, const float*, int64_t, int64_t, const int64_t*, hipStream_t);
@@ -62,9 +39,6 @@ int launch_cd_loss_seed(const float*, int64_t, float, const float*, const float*
 int launch_pcd_start_points(const float*, int64_t, int32_t, float*, int64_t, int64_t, int64_t, float, uint64_t, uint64_t, const uint64_t*,
                             hipStream_t);
 int launch_noise_fill(float*, int64_t, int32_t, uint64_t, uint64_t, const uint64_t*, hipStream_t);
-int launch_langevin_chain_mlp(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, float, float, float, const float*,
-                              int, float, float, int32_t, float*, const float*, uint64_t, uint64_t, float*, hipStream_t,
-                              const uint64_t* rng_dev = nullptr);
 int launch_energy_grad_mlp(const ebm_energy_t&, const float*, int64_t, int32_t, float*, float*, hipStream_t);
 int launch_mlp_backward_acts(int32_t, const float*, const float*, int64_t, int32_t, const float*, float*, float*, float*, hipStream_t, const char*);
 int64_t mlp_param_grads_work_floats(int32_t hidden, int32_t dim, int64_t n);  // mlp_param_grads.hip
@@ -75,41 +49,7 @@ size_t mlp_w1_image_bytes(int32_t hidden, int32_t dim);  // mlp_wide_slab.hip
 int launch_mlp_w1_image(const float* params, int32_t hidden, int32_t dim, void* image, hipStream_t st, const char* who);
 size_t gauss_prec_image_bytes(int32_t dim);  // gauss_big_img.hip
 int launch_gauss_prec_image(const float* prec, int32_t dim, void* image, hipStream_t st, const char* who);
-bool gauss_mfma_supported(int32_t dim);
-bool gauss_lds5_supported(int32_t dim);   // gauss_mfma.hip: 132 .. 160, Ps resident in LDS (plain Langevin call)
-int32_t gauss_pack_factor(int32_t dim, int64_t n_chains);  // gauss_mfma.hip: 1 as is, > 1 packed rows, 0 no matrix-layout form
-bool gauss_big_supported(int32_t dim);                      // gauss_big.hip: dims 132 .. 512 in steps of 4, tiled per step
-int launch_langevin_chain_gauss_big(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, float, float, float,
-                                    const float*, int, float, float, int32_t, float*, const float*, uint64_t, uint64_t,
-                                    float*, hipStream_t);
-bool gauss_big_diag_plan(int64_t, int32_t, diag::DiagArgs&);  // gauss_big.hip: one record per wave-tile of 32 chains
 int launch_energy_grad_gauss_big(const ebm_energy_t&, const float*, int64_t, int32_t, float*, float*, hipStream_t);
-bool gmm_mfma_supported(int32_t dim, int32_t n_comp);
-bool matrix_langevin_diag_plan(const ebm_energy_t&, int64_t, int32_t, diag::DiagArgs&);
-int launch_langevin_chain_matrix_diag(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, float, float, float,
-                                      const float*, int, float, float, int32_t, float*, const float*, uint64_t, uint64_t,
-                                      float*, hipStream_t);
-int launch_langevin_chain_gmm_mfma(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, float, float, float,
-                                   const float*, int, float, float, int32_t, float*, const float*, uint64_t, uint64_t,
-                                   hipStream_t);
-bool gauss_res_shift_supported(const ebm_energy_t& e, int32_t dim);  // gauss_res_shift.hip: widths off multiples of 4 up to 254, per-class images
-int launch_langevin_chain_gauss_res_shift(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, float, float, float,
-                                          const float*, int, float, float, int32_t, float*, const float*, uint64_t, uint64_t, float*, hipStream_t);
-bool gmm_wide_supported(int32_t dim, int32_t n_comp);        // gmm_wide.hip: mixtures at 132 .. 256 dims (five to eight tiles)
-bool gmm_wide_shift_supported(int32_t dim, int32_t n_comp);  // gmm_wide_shift.hip: ... and the widths off multiples of 4 between 126 and 254
-int launch_langevin_chain_gmm_wide(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, float, float, float,
-                                   const float*, int, float, float, int32_t, float*, const float*, uint64_t, uint64_t, float*, hipStream_t);
-int launch_langevin_chain_gmm_wide_shift(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, float, float, float,
-                                         const float*, int, float, float, int32_t, float*, const float*, uint64_t, uint64_t, float*, hipStream_t);
-bool gmm_shift_supported(int32_t dim, int32_t n_comp);  // gmm_shift.hip: mixtures at widths off multiples of 4, 21 .. 125
-int launch_langevin_chain_gmm_shift(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, float, float, float,
-                                    const float*, int, float, float, int32_t, float*, const float*, uint64_t, uint64_t, float*, hipStream_t);
-bool gauss_shift_supported(int32_t dim);  // gauss_shift.hip: widths off multiples of 4, 21 .. 157, on shifted rows
-int launch_langevin_chain_gauss_shift(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, float, float, float,
-                                      const float*, int, float, float, int32_t, float*, const float*, uint64_t, uint64_t, float*, hipStream_t);
-int launch_langevin_chain_gauss_mfma(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, float, float, float,
-                                     const float*, int, float, float, int32_t, float*, const float*, uint64_t, uint64_t,
-                                     hipStream_t);
 
 namespace {
 thread_local char g_err[512] = "";
@@ -249,11 +189,14 @@ int ebm_langevin_step_dev_f32(const float* x, const float* grad, float* out, int
                               rng_state, (hipStream_t)stream);
 }
 
-static int langevin_chain_impl(const char* who, int heun, const ebm_energy_t* energy, float* x, int64_t n_chains,
+// The three Langevin chain entries: validate, decode the flag word, build the request -- once, here -- then route it.
+// `dev_rng`: ebm_langevin_chain_dev_f32 (RNG coordinates in device memory, MLP energies only; the MLP kernels never contract,
+// so EBM_CHAIN_CONTRACTED is accepted there and ignored).
+static int langevin_chain_impl(const char* who, int heun, bool dev_rng, const ebm_energy_t* energy, float* x, int64_t n_chains,
                                int32_t dim, int32_t k_steps, float eta, float sqrt_eta, float noise_coef,
-                               const float* coef_table, int32_t clamp_on, float cmin, float cmax,
-                               int32_t thin, float* traj, float* diag_partials, const float* noise, uint64_t seed,
-                               uint64_t offset, void* stream) {
+                               const float* coef_table, int32_t clamp_on, float cmin, float cmax, int32_t thin, float* traj,
+                               float* diag_partials, const float* noise, uint64_t seed, uint64_t offset,
+                               const uint64_t* rng_state, void* stream) {
   if (int r = check_energy(energy, dim, who)) return r;
   if (heun) {
     if (int r = reject_mlp(energy, who)) return r;
@@ -261,100 +204,75 @@ static int langevin_chain_impl(const char* who, int heun, const ebm_energy_t* en
   if (int r = check_state(x, n_chains, dim, who)) return r;
   // ABI 8: `clamp_on` is a flag word -- bit 0 the clamp, bit 1 EBM_CHAIN_CONTRACTED (include/ebm_hip.h)
   if (clamp_on & ~(EBM_CHAIN_CLAMP | EBM_CHAIN_CONTRACTED)) return fail(EBM_EINVAL, "%s: unknown bits in clamp_on (%d)", who, clamp_on);
-  const int contracted = (clamp_on & EBM_CHAIN_CONTRACTED) != 0;
-  clamp_on &= EBM_CHAIN_CLAMP;
   if (k_steps < 0 || thin < 1) return fail(EBM_EINVAL, "%s: k_steps=%d thin=%d", who, k_steps, thin);
+  if (dev_rng) {
+    if (!rng_state) return fail(EBM_EINVAL, "%s: rng_state is NULL", who);
+    if (energy->kind != EBM_ENERGY_MLP)
+      return fail(EBM_EKIND, "%s: device-resident RNG coordinates are taken by the EBM_ENERGY_MLP chain kernels only", who);
+  }
   if (n_chains == 0 || k_steps == 0) return 0;
   if ((coef_table && !aligned16(coef_table)) || (traj && !aligned16(traj)) || (noise && !aligned16(noise)) ||
       (diag_partials && !aligned16(diag_partials)))
     return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
-  if (diag_partials && k_steps / thin > 0) {
+  if (k_steps / thin == 0) diag_partials = nullptr;
+  const LangevinChainReq q{*energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef, coef_table,
+                           (clamp_on & EBM_CHAIN_CLAMP) != 0, (clamp_on & EBM_CHAIN_CONTRACTED) != 0, cmin, cmax, thin, traj,
+                           noise, seed, offset, diag_partials, heun, rng_state};
+  const ebm_energy_t& e = *energy;
+  const hipStream_t st = (hipStream_t)stream;
+  if (diag_partials) {
     diag::DiagArgs d;
-    const DiagFamily fam = plan_diag(*energy, heun ? EBM_DIAG_LANGEVIN_HEUN : EBM_DIAG_LANGEVIN, n_chains, dim, noise != nullptr,
-                                     traj != nullptr, d);
-    if (fam == kDiagElemFlat)
-      return launch_langevin_chain_elem_diag(energy->kind, energy->s[0], energy->s[1], x, n_chains, dim, k_steps, eta, sqrt_eta,
-                                             noise_coef, coef_table, clamp_on, cmin, cmax, thin, traj, seed, offset, heun,
-                                             diag_partials, (hipStream_t)stream);
-    if (fam == kDiagRows)
-      return launch_langevin_chain_rows(*energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef, coef_table, clamp_on, cmin,
-                                        cmax, thin, traj, noise, seed, offset, heun, diag_partials, (hipStream_t)stream);
-    if (fam == kDiagMlp)
-      return launch_langevin_chain_mlp(*energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef, coef_table, clamp_on, cmin, cmax,
-                                       thin, traj, noise, seed, offset, diag_partials, (hipStream_t)stream);
-    if (fam == kDiagGaussBig)
-      return launch_langevin_chain_gauss_big(*energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef, coef_table, clamp_on, cmin,
-                                             cmax, thin, traj, noise, seed, offset, diag_partials, (hipStream_t)stream);
-    if (fam == kDiagMatrix)
-      return launch_langevin_chain_matrix_diag(*energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef, coef_table, clamp_on,
-                                               cmin, cmax, thin, traj, noise, seed, offset, diag_partials, (hipStream_t)stream);
-    return fail(energy->kind == EBM_ENERGY_MLP ? EBM_EKIND : EBM_EDIM,
-                "%s: no in-kernel diagnostics for this energy / dim %d (see ebm_diag_layout)", who, dim);
+    switch (plan_diag(e, heun ? EBM_DIAG_LANGEVIN_HEUN : EBM_DIAG_LANGEVIN, n_chains, dim, noise != nullptr, traj != nullptr, d)) {
+      case kDiagElemFlat: return launch_langevin_chain_elem_diag(q, st);
+      case kDiagRows: return launch_langevin_chain_rows(q, st);
+      case kDiagMlp: return launch_langevin_chain_mlp(q, st);
+      case kDiagGaussBig: return launch_langevin_chain_gauss_big(q, st);
+      case kDiagMatrix: return launch_langevin_chain_matrix_diag(q, st);
+      default:
+        return fail(e.kind == EBM_ENERGY_MLP ? EBM_EKIND : EBM_EDIM,
+                    "%s: no in-kernel diagnostics for this energy / dim %d (see ebm_diag_layout)", who, dim);
+    }
   }
-  if (energy->kind == EBM_ENERGY_MLP)
-    return launch_langevin_chain_mlp(*energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef, coef_table,
-                                     clamp_on, cmin, cmax, thin, traj, noise, seed, offset, nullptr, (hipStream_t)stream);
-  if (energy->kind == EBM_ENERGY_DOUBLE_WELL || energy->kind == EBM_ENERGY_HARMONIC)
-    return launch_langevin_chain_elem(energy->kind, energy->s[0], energy->s[1], x, n_chains, dim,
-                                      k_steps, eta, sqrt_eta, noise_coef, coef_table, clamp_on, cmin,
-                                      cmax, thin, traj, noise, seed, offset, heun, contracted, (hipStream_t)stream);
-  if (!heun && energy->kind == EBM_ENERGY_GAUSSIAN && gauss_shift_supported(dim)) {
+  if (e.kind == EBM_ENERGY_MLP) return launch_langevin_chain_mlp(q, st);
+  if (e.kind == EBM_ENERGY_DOUBLE_WELL || e.kind == EBM_ENERGY_HARMONIC) return launch_langevin_chain_elem(q, st);
+  if (!heun && e.kind == EBM_ENERGY_GAUSSIAN && gauss_shift_supported(dim)) {
     // A/B switch: EBM_GAUSS_NOSHIFT=1 keeps the packed rows / the lane-group kernel for widths off multiples of 4
     static const bool no_shift = ab_switch("EBM_GAUSS_NOSHIFT");
-    if (!no_shift)
-      return launch_langevin_chain_gauss_shift(*energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef, coef_table,
-                                               clamp_on, cmin, cmax, thin, traj, noise, seed, offset, nullptr, (hipStream_t)stream);
+    if (!no_shift) return launch_langevin_chain_gauss_shift(q, st);
   }
-  if (!heun && gauss_res_shift_supported(*energy, dim)) {
+  if (!heun && gauss_res_shift_supported(e, dim)) {
     static const bool no_shift = ab_switch("EBM_GAUSS_NOSHIFT");
-    if (!no_shift)
-      return launch_langevin_chain_gauss_res_shift(*energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef, coef_table,
-                                                   clamp_on, cmin, cmax, thin, traj, noise, seed, offset, nullptr, (hipStream_t)stream);
+    if (!no_shift) return launch_langevin_chain_gauss_res_shift(q, st);
   }
-  if (!heun && energy->kind == EBM_ENERGY_GAUSSIAN && gauss_pack_factor(dim, n_chains) >= 1) {
+  if (!heun && e.kind == EBM_ENERGY_GAUSSIAN && gauss_pack_factor(dim, n_chains) >= 1) {
     // A/B switch for tests and profiling: EBM_GAUSS_ROWS=1 keeps the LDS mat-vec kernel
     static const bool force_rows = ab_switch("EBM_GAUSS_ROWS");
-    if (!force_rows)
-      return launch_langevin_chain_gauss_mfma(*energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef, coef_table,
-                                              clamp_on, cmin, cmax, thin, traj, noise, seed, offset, (hipStream_t)stream);
+    if (!force_rows) return launch_langevin_chain_gauss_mfma(q, st);
   }
-  if (!heun && energy->kind == EBM_ENERGY_GAUSSIAN && gauss_lds5_supported(dim)) {
+  if (!heun && e.kind == EBM_ENERGY_GAUSSIAN && gauss_lds5_supported(dim)) {
     static const bool force_big = ab_switch("EBM_GAUSS_NO_LDS5");
-    if (!force_big)
-      return launch_langevin_chain_gauss_mfma(*energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef, coef_table,
-                                              clamp_on, cmin, cmax, thin, traj, noise, seed, offset, (hipStream_t)stream);
+    if (!force_big) return launch_langevin_chain_gauss_mfma(q, st);
   }
-  if (!heun && energy->kind == EBM_ENERGY_GAUSSIAN && gauss_big_supported(dim)) {
+  if (!heun && e.kind == EBM_ENERGY_GAUSSIAN && gauss_big_supported(dim)) {
     static const bool force_rows = ab_switch("EBM_GAUSS_ROWS");
-    if (!force_rows)
-      return launch_langevin_chain_gauss_big(*energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef, coef_table,
-                                             clamp_on, cmin, cmax, thin, traj, noise, seed, offset, nullptr, (hipStream_t)stream);
+    if (!force_rows) return launch_langevin_chain_gauss_big(q, st);
   }
-  if (!heun && energy->kind == EBM_ENERGY_GMM && (gmm_wide_supported(dim, energy->n_comp) || gmm_wide_shift_supported(dim, energy->n_comp))) {
+  if (!heun && e.kind == EBM_ENERGY_GMM && (gmm_wide_supported(dim, e.n_comp) || gmm_wide_shift_supported(dim, e.n_comp))) {
     static const bool no_wide = ab_switch("EBM_GMM_NOWIDE");  // A/B switch: the lane-group kernels above 128 dims
     if (!no_wide)
-      return (gmm_wide_supported(dim, energy->n_comp) ? launch_langevin_chain_gmm_wide : launch_langevin_chain_gmm_wide_shift)(
-          *energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef, coef_table, clamp_on, cmin, cmax, thin, traj, noise, seed, offset,
-          nullptr, (hipStream_t)stream);
+      return gmm_wide_supported(dim, e.n_comp) ? launch_langevin_chain_gmm_wide(q, st) : launch_langevin_chain_gmm_wide_shift(q, st);
   }
-  if (!heun && energy->kind == EBM_ENERGY_GMM && gmm_shift_supported(dim, energy->n_comp)) {
+  if (!heun && e.kind == EBM_ENERGY_GMM && gmm_shift_supported(dim, e.n_comp)) {
     static const bool no_shift = ab_switch("EBM_GAUSS_NOSHIFT");
-    if (!no_shift)
-      return launch_langevin_chain_gmm_shift(*energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef, coef_table,
-                                             clamp_on, cmin, cmax, thin, traj, noise, seed, offset, nullptr, (hipStream_t)stream);
+    if (!no_shift) return launch_langevin_chain_gmm_shift(q, st);
   }
   // mixtures of up to 32 components on the matrix layout (gauss_mfma.hip / gmm_bf16x3.h); dims 16 / 32 with K <= 8 keep
   // one lane per chain with the means as scalar operands
-  if (!heun && energy->kind == EBM_ENERGY_GMM && gmm_mfma_supported(dim, energy->n_comp) &&
-      !(dim == 32 && energy->n_comp <= 8)) {
+  if (!heun && e.kind == EBM_ENERGY_GMM && gmm_mfma_supported(dim, e.n_comp) && !(dim == 32 && e.n_comp <= 8)) {
     static const bool force_rows = ab_switch("EBM_GMM_ROWS");
-    if (!force_rows)
-      return launch_langevin_chain_gmm_mfma(*energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef, coef_table,
-                                            clamp_on, cmin, cmax, thin, traj, noise, seed, offset, (hipStream_t)stream);
+    if (!force_rows) return launch_langevin_chain_gmm_mfma(q, st);
   }
-  return launch_langevin_chain_rows(*energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef,
-                                    coef_table, clamp_on, cmin, cmax, thin, traj, noise, seed, offset,
-                                    heun, nullptr, (hipStream_t)stream);
+  return launch_langevin_chain_rows(q, st);
 }
 
 int ebm_langevin_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_chains, int32_t dim,
@@ -362,26 +280,16 @@ int ebm_langevin_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_chain
                            const float* coef_table, int32_t clamp_on, float cmin, float cmax,
                            int32_t thin, float* traj, float* diag_partials, const float* noise, uint64_t seed,
                            uint64_t offset, void* stream) {
-  return langevin_chain_impl("ebm_langevin_chain_f32", 0, energy, x, n_chains, dim, k_steps, eta, sqrt_eta,
-                             noise_coef, coef_table, clamp_on, cmin, cmax, thin, traj, diag_partials, noise, seed, offset, stream);
+  return langevin_chain_impl("ebm_langevin_chain_f32", 0, false, energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef,
+                             coef_table, clamp_on, cmin, cmax, thin, traj, diag_partials, noise, seed, offset, nullptr, stream);
 }
 
 int ebm_langevin_chain_dev_f32(const ebm_energy_t* energy, float* x, int64_t n_chains, int32_t dim, int32_t k_steps,
                                float eta, float sqrt_eta, float noise_coef, const float* coef_table, int32_t clamp_on,
                                float cmin, float cmax, int32_t thin, float* traj, const uint64_t* rng_state,
                                uint64_t step_delta, void* stream) {
-  const char* who = "ebm_langevin_chain_dev_f32";
-  if (int r = check_energy(energy, dim, who)) return r;
-  if (int r = check_state(x, n_chains, dim, who)) return r;
-  if (k_steps < 0 || thin < 1) return fail(EBM_EINVAL, "%s: k_steps=%d thin=%d", who, k_steps, thin);
-  if (!rng_state) return fail(EBM_EINVAL, "%s: rng_state is NULL", who);
-  if (energy->kind != EBM_ENERGY_MLP)
-    return fail(EBM_EKIND, "%s: device-resident RNG coordinates are taken by the EBM_ENERGY_MLP chain kernels only", who);
-  if (n_chains == 0 || k_steps == 0) return 0;
-  if ((coef_table && !aligned16(coef_table)) || (traj && !aligned16(traj)))
-    return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
-  return launch_langevin_chain_mlp(*energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef, coef_table, clamp_on, cmin, cmax,
-                                   thin, traj, nullptr, 0, step_delta, nullptr, (hipStream_t)stream, rng_state);
+  return langevin_chain_impl("ebm_langevin_chain_dev_f32", 0, true, energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef,
+                             coef_table, clamp_on, cmin, cmax, thin, traj, nullptr, nullptr, 0, step_delta, rng_state, stream);
 }
 
 int ebm_langevin_heun_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_chains, int32_t dim,
@@ -389,17 +297,16 @@ int ebm_langevin_heun_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_
                                 const float* coef_table, int32_t clamp_on, float cmin, float cmax,
                                 int32_t thin, float* traj, float* diag_partials, const float* noise, uint64_t seed,
                                 uint64_t offset, void* stream) {
-  return langevin_chain_impl("ebm_langevin_heun_chain_f32", 1, energy, x, n_chains, dim, k_steps, eta, sqrt_eta,
-                             noise_coef, coef_table, clamp_on, cmin, cmax, thin, traj, diag_partials, noise, seed, offset, stream);
+  return langevin_chain_impl("ebm_langevin_heun_chain_f32", 1, false, energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef,
+                             coef_table, clamp_on, cmin, cmax, thin, traj, diag_partials, noise, seed, offset, nullptr, stream);
 }
 
-int ebm_hmc_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_chains, int32_t dim,
-                      int32_t n_mh, int32_t n_leapfrog, float eps, const float* eps_table,
-                      int32_t mass_kind, double mass_scalar, const float* mass_diag, int32_t thin,
-                      float* traj, float* diag_partials, uint8_t* accept_mask, uint32_t* accept_count,
-                      const float* p_noise, const float* u, uint64_t seed, uint64_t offset,
-                      void* stream) {
-  const char* who = "ebm_hmc_chain_f32";
+// The two HMC chain entries: validate and build the request once, then route it.
+static int hmc_chain_impl(const char* who, bool audit, const ebm_energy_t* energy, float* x, int64_t n_chains, int32_t dim,
+                          int32_t n_mh, int32_t n_leapfrog, float eps, const float* eps_table, int32_t mass_kind, double mass_scalar,
+                          const float* mass_diag, int32_t thin, float* traj, float* diag_partials, uint8_t* accept_mask,
+                          uint32_t* accept_count, const float* p_noise, const float* u, uint64_t seed, uint64_t offset,
+                          void* stream) {
   if (int r = check_energy(energy, dim, who)) return r;
   if (int r = check_state(x, n_chains, dim, who)) return r;
   if (n_mh < 0 || thin < 1 || n_leapfrog < 1)
@@ -412,6 +319,10 @@ int ebm_hmc_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_chains, in
   if ((traj && !aligned16(traj)) || (p_noise && !aligned16(p_noise)) || (diag_partials && !aligned16(diag_partials)))
     return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
   if (n_mh / thin == 0) diag_partials = nullptr;
+  const HmcChainReq q{*energy, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar, mass_diag, thin, traj,
+                      accept_mask, accept_count, p_noise, u, seed, offset, diag_partials};
+  const hipStream_t st = (hipStream_t)stream;
+  if (audit) return launch_hmc_chain_audit(q, st);
   if (diag_partials) {
     diag::DiagArgs d;
     const DiagFamily fam = plan_diag(*energy, EBM_DIAG_HMC, n_chains, dim, p_noise != nullptr, traj != nullptr, d);
@@ -419,31 +330,26 @@ int ebm_hmc_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_chains, in
       return fail(energy->kind == EBM_ENERGY_MLP ? EBM_EKIND : EBM_EDIM,
                   "%s: no in-kernel diagnostics for this energy / dim %d (see ebm_diag_layout)", who, dim);
   }
-  if (energy->kind == EBM_ENERGY_MLP)
-    return launch_hmc_chain_mlp(*energy, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar,
-                                mass_diag, thin, traj, accept_mask, accept_count, p_noise, u, seed, offset, diag_partials,
-                                (hipStream_t)stream);
-  return launch_hmc_chain(*energy, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind,
-                          mass_scalar, mass_diag, thin, traj, accept_mask, accept_count, p_noise, u,
-                          seed, offset, diag_partials, (hipStream_t)stream);
+  if (energy->kind == EBM_ENERGY_MLP) return launch_hmc_chain_mlp(q, st);
+  return launch_hmc_chain(q, st);
+}
+
+int ebm_hmc_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_chains, int32_t dim,
+                      int32_t n_mh, int32_t n_leapfrog, float eps, const float* eps_table,
+                      int32_t mass_kind, double mass_scalar, const float* mass_diag, int32_t thin,
+                      float* traj, float* diag_partials, uint8_t* accept_mask, uint32_t* accept_count,
+                      const float* p_noise, const float* u, uint64_t seed, uint64_t offset,
+                      void* stream) {
+  return hmc_chain_impl("ebm_hmc_chain_f32", false, energy, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar,
+                        mass_diag, thin, traj, diag_partials, accept_mask, accept_count, p_noise, u, seed, offset, stream);
 }
 
 int ebm_hmc_chain_audit_f32(const ebm_energy_t* energy, float* x, int64_t n_chains, int32_t dim, int32_t n_mh, int32_t n_leapfrog,
                             float eps, const float* eps_table, int32_t mass_kind, double mass_scalar, const float* mass_diag,
                             int32_t thin, float* traj, uint8_t* accept_mask, uint32_t* accept_count, const float* p_noise,
                             const float* u, uint64_t seed, uint64_t offset, void* stream) {
-  const char* who = "ebm_hmc_chain_audit_f32";
-  if (int r = check_energy(energy, dim, who)) return r;
-  if (int r = check_state(x, n_chains, dim, who)) return r;
-  if (n_mh < 0 || thin < 1 || n_leapfrog < 1)
-    return fail(EBM_EINVAL, "%s: n_mh=%d thin=%d n_leapfrog=%d", who, n_mh, thin, n_leapfrog);
-  if (mass_kind < EBM_MASS_NONE || mass_kind > EBM_MASS_DIAG || (mass_kind == EBM_MASS_DIAG && !mass_diag))
-    return fail(EBM_EINVAL, "%s: bad mass specification (kind %d)", who, mass_kind);
-  if ((p_noise == nullptr) != (u == nullptr)) return fail(EBM_EINVAL, "%s: p_noise and u must be given together", who);
-  if (n_chains == 0 || n_mh == 0) return 0;
-  if ((traj && !aligned16(traj)) || (p_noise && !aligned16(p_noise))) return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
-  return launch_hmc_chain_audit(*energy, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar, mass_diag, thin, traj,
-                                accept_mask, accept_count, p_noise, u, seed, offset, (hipStream_t)stream);
+  return hmc_chain_impl("ebm_hmc_chain_audit_f32", true, energy, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind,
+                        mass_scalar, mass_diag, thin, traj, nullptr, accept_mask, accept_count, p_noise, u, seed, offset, stream);
 }
 
 int ebm_leapfrog_kick_drift_f32(const float* x, const float* p, const float* force, float* x_new,

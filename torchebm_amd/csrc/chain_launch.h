@@ -1,0 +1,147 @@
+// Host-side requests of the fused Langevin and HMC chain calls, and the one declaration of every chain launcher.
+// The C-ABI entries (api.hip) validate a call and decode it into a request once; a launcher fills its kernel's own
+// argument struct from the request.  A request never reaches a kernel.
+#pragma once
+#include <cmath>
+
+#include "diag.h"
+#include "ebm_common.h"
+
+namespace ebm {
+
+struct LangevinChainReq {
+  const ebm_energy_t& e;
+  float* x;
+  int64_t n_chains;
+  int32_t dim, k_steps;
+  float eta, sqrt_eta, noise_coef;
+  const float* coef_table;
+  bool clamp, contracted;  // the flag word `clamp_on`, decoded: EBM_CHAIN_CLAMP, EBM_CHAIN_CONTRACTED
+  float cmin, cmax;
+  int32_t thin;
+  float* traj;
+  const float* noise;
+  uint64_t seed, offset;
+  float* diag_partials;     // null when no step is kept
+  int heun;
+  const uint64_t* rng_dev;  // ebm_langevin_chain_dev_f32: {seed, step} in device memory (MLP kernels only), else null
+
+  RngKey key() const { return RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)}; }
+  int32_t n_kept() const { return k_steps / thin; }
+};
+
+struct HmcChainReq {
+  const ebm_energy_t& e;
+  float* x;
+  int64_t n_chains;
+  int32_t dim, n_mh, n_leapfrog;
+  float eps;
+  const float* eps_table;
+  int32_t mass_kind;
+  double mass_scalar;
+  const float* mass_diag;
+  int32_t thin;
+  float* traj;
+  uint8_t* accept_mask;
+  uint32_t* accept_count;
+  const float* p_noise;
+  const float* u;
+  uint64_t seed, offset;
+  float* diag_partials;  // null when no transition is kept
+
+  RngKey key() const { return RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)}; }
+  int32_t n_kept() const { return n_mh / thin; }
+};
+
+// The fields the row-major Langevin argument structs share (GaussArgs, BigArgs, RowChainArgs, WideArgs).
+template <class Args>
+inline void fill_langevin(Args& a, const LangevinChainReq& q) {
+  a.x = q.x; a.n_chains = q.n_chains; a.dim = q.dim; a.k_steps = q.k_steps;
+  a.eta = q.eta; a.sqrt_eta = q.sqrt_eta; a.noise_coef = q.noise_coef;
+  a.table = reinterpret_cast<const float4*>(q.coef_table);
+  a.clamp_on = q.clamp; a.cmin = q.cmin; a.cmax = q.cmax;
+  a.thin = q.thin; a.n_kept = q.n_kept(); a.traj = q.traj; a.noise = q.noise;
+  a.key = q.key(); a.step0 = q.offset;
+}
+
+// The fields the HMC argument structs share (HmcArgs, GaussHmcArgs, WideHmcArgs), the scalar mass in its three forms.
+template <class Args>
+inline void fill_hmc(Args& a, const HmcChainReq& q) {
+  a.x = q.x; a.n_chains = q.n_chains; a.dim = q.dim; a.n_mh = q.n_mh; a.n_leapfrog = q.n_leapfrog;
+  a.eps = q.eps; a.eps_table = q.eps_table;
+  a.mass_raw = (float)q.mass_scalar;
+  a.mass_sqrt = (float)sqrt(q.mass_scalar);
+  a.mass_safe = (float)(q.mass_scalar < 1e-10 ? 1e-10 : q.mass_scalar);
+  a.thin = q.thin; a.n_kept = q.n_kept(); a.traj = q.traj;
+  a.accept_mask = q.accept_mask; a.accept_count = q.accept_count; a.p_noise = q.p_noise; a.u = q.u;
+  a.key = q.key(); a.step0 = q.offset;
+}
+
+// ---------------------------------------------------------------------------------
+// Langevin chain launchers and the predicates that route to them
+// ---------------------------------------------------------------------------------
+int launch_langevin_chain_elem(const LangevinChainReq&, hipStream_t);       // langevin.hip: double well, harmonic
+int launch_langevin_chain_elem_diag(const LangevinChainReq&, hipStream_t);  // langevin_diag.hip: ... with records
+bool elem_diag_supported(int32_t dim, bool has_noise, bool has_traj);
+bool elem_diag_plan(int64_t n_chains, int32_t dim, diag::DiagArgs&);
+int launch_langevin_chain_rows(const LangevinChainReq&, hipStream_t);       // rows_langevin.hip: the lane-group kernels
+bool rows_langevin_diag_plan(const ebm_energy_t&, int heun, int64_t n_chains, int32_t dim, diag::DiagArgs&);
+int launch_langevin_chain_mlp(const LangevinChainReq&, hipStream_t);        // mlp.hip
+int launch_mlp_wide(const LangevinChainReq&, float* energy_out, float* grad_out, hipStream_t, const char* who);  // mlp_wide.hip
+bool mlp_wide_supported(int32_t hidden, int32_t dim);
+bool mlp_diag_plan(const ebm_energy_t&, bool hmc, int64_t n_chains, int32_t dim, diag::DiagArgs&);
+// gauss_mfma.hip: dims 20 .. 128 (multiples of 4), other widths as packed rows, 132 .. 160 with Ps resident in LDS
+int launch_langevin_chain_gauss_mfma(const LangevinChainReq&, hipStream_t);
+bool gauss_mfma_supported(int32_t dim);
+bool gauss_lds5_supported(int32_t dim);
+int32_t gauss_pack_factor(int32_t dim, int64_t n_chains);  // 1 as is, > 1 packed rows, 0 no matrix-layout form
+int launch_langevin_chain_gmm_mfma(const LangevinChainReq&, hipStream_t);  // gauss_mfma.hip: mixtures up to 32 components
+bool gmm_mfma_supported(int32_t dim, int32_t n_comp);
+int launch_langevin_chain_matrix_diag(const LangevinChainReq&, hipStream_t);  // gauss_mfma.hip: records of the matrix layout
+bool matrix_langevin_diag_plan(const ebm_energy_t&, int64_t n_chains, int32_t dim, diag::DiagArgs&);
+int launch_langevin_chain_gauss_shift(const LangevinChainReq&, hipStream_t);  // gauss_shift.hip: widths off multiples of 4, 21 .. 157
+bool gauss_shift_supported(int32_t dim);
+int launch_langevin_chain_gauss_res_shift(const LangevinChainReq&, hipStream_t);  // gauss_res_shift.hip: ... up to 254, per-class images
+bool gauss_res_shift_supported(const ebm_energy_t&, int32_t dim);
+int launch_langevin_chain_gauss_big(const LangevinChainReq&, hipStream_t);  // gauss_big.hip: dims 132 .. 512 in steps of 4
+bool gauss_big_supported(int32_t dim);
+bool gauss_big_diag_plan(int64_t n_chains, int32_t dim, diag::DiagArgs&);
+int launch_langevin_chain_gmm_shift(const LangevinChainReq&, hipStream_t);  // gmm_shift.hip: mixtures off multiples of 4, 21 .. 125
+bool gmm_shift_supported(int32_t dim, int32_t n_comp);
+int launch_langevin_chain_gmm_wide(const LangevinChainReq&, hipStream_t);        // gmm_wide.hip: mixtures at 132 .. 256 dims
+int launch_langevin_chain_gmm_wide_shift(const LangevinChainReq&, hipStream_t);  // gmm_wide_shift.hip: ... and the widths between
+bool gmm_wide_supported(int32_t dim, int32_t n_comp);
+bool gmm_wide_shift_supported(int32_t dim, int32_t n_comp);
+
+// ---------------------------------------------------------------------------------
+// HMC chain launchers and the predicates that route to them
+// ---------------------------------------------------------------------------------
+int launch_hmc_chain(const HmcChainReq&, hipStream_t);        // hmc.hip: routing, then the lane-group kernels
+int launch_hmc_chain_audit(const HmcChainReq&, hipStream_t);  // hmc.hip: the literal leapfrog sequence
+bool hmc_diag_plan(const ebm_energy_t&, int64_t n_chains, int32_t dim, diag::DiagArgs&);
+int launch_hmc_chain_mlp(const HmcChainReq&, hipStream_t);  // mlp.hip
+int launch_hmc_chain_mlp_wide(const HmcChainReq&, hipStream_t, const char* who);  // mlp_wide_hmc.hip
+bool mlp_wide_hmc_supported(int32_t hidden, int32_t dim);
+int launch_hmc_chain_gauss_mfma(const HmcChainReq&, hipStream_t);  // gauss_hmc_mfma.hip: dims 20 .. 160 (multiples of 4)
+bool gauss_hmc_mfma_supported(int32_t dim, int32_t mass_kind);
+int launch_hmc_chain_gauss_shift(const HmcChainReq&, hipStream_t);       // gauss_hmc_shift.hip: widths off multiples of 4, 17 .. 158
+int launch_hmc_chain_gauss_shift_diag(const HmcChainReq&, hipStream_t);  // gauss_hmc_shift_diag.hip: ... with records
+bool gauss_hmc_shift_supported(int32_t dim);
+int launch_hmc_chain_gauss_stream(const HmcChainReq&, hipStream_t);  // gauss_hmc_stream.hip: dims 164 .. 256 with the pre-split image
+bool gauss_hmc_stream_supported(const ebm_energy_t&, int32_t dim);
+int launch_hmc_chain_gauss_stream_shift(const HmcChainReq&, hipStream_t);       // gauss_hmc_stream_shift.hip: ... the widths between
+int launch_hmc_chain_gauss_stream_shift_diag(const HmcChainReq&, hipStream_t);  // gauss_hmc_stream_shift_diag.hip: ... with records
+bool gauss_hmc_stream_shift_supported(const ebm_energy_t&, int32_t dim);
+int launch_hmc_chain_gmm_mfma(const HmcChainReq&, hipStream_t);  // gmm_hmc_mfma.hip: mixtures up to 32 components, dims up to 128
+bool gmm_hmc_mfma_supported(int32_t dim, int32_t n_comp, int32_t mass_kind);
+int launch_hmc_chain_gmm_shift(const HmcChainReq&, hipStream_t);       // gmm_hmc_shift.hip: mixtures off multiples of 4
+int launch_hmc_chain_gmm_shift_diag(const HmcChainReq&, hipStream_t);  // gmm_hmc_shift_diag.hip: ... with records
+bool gmm_hmc_shift_supported(int32_t dim, int32_t n_comp, int32_t mass_kind, bool records);
+int launch_hmc_chain_gmm_wide(const HmcChainReq&, hipStream_t);        // gmm_hmc_wide.hip: mixtures at 132 .. 224 dims
+int launch_hmc_chain_gmm_wide_shift(const HmcChainReq&, hipStream_t);  // gmm_hmc_wide_shift.hip: ... and the widths between
+bool gmm_hmc_wide_supported(int32_t dim, int32_t n_comp, int32_t mass_kind);
+bool gmm_hmc_wide_shift_supported(int32_t dim, int32_t n_comp, int32_t mass_kind);
+int launch_hmc_chain_matrix_diag(const HmcChainReq&, hipStream_t);  // matrix_hmc_diag.hip: records of the matrix layout
+bool matrix_hmc_diag_plan(const ebm_energy_t&, int64_t n_chains, int32_t dim, diag::DiagArgs&);
+
+}  // namespace ebm

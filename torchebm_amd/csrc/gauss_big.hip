@@ -44,26 +44,18 @@ bool gauss_big_diag_plan(int64_t n_chains, int32_t dim, diag::DiagArgs& d) {
   return gauss_big_supported(dim) && diag::plan(n_chains, dim, 32 * (int64_t)dim, d);
 }
 
-int launch_langevin_chain_gauss_big(const ebm_energy_t& e, float* x, int64_t n_chains, int32_t dim, int32_t k_steps,
-                                    float eta, float sqrt_eta, float noise_coef, const float* coef_table,
-                                    int clamp_on, float cmin, float cmax, int32_t thin, float* traj,
-                                    const float* noise, uint64_t seed, uint64_t offset, float* diag_partials, hipStream_t st) {
+int launch_langevin_chain_gauss_big(const LangevinChainReq& q, hipStream_t st) {
+  const int32_t dim = q.dim;
   if (!gauss_big_supported(dim)) return fail(EBM_EDIM, "ebm_langevin_chain_f32: the tiled Gaussian kernel takes dims 132 .. 512 in steps of 4, not %d", dim);
   BigArgs a{};
-  a.x = x; a.n_chains = n_chains; a.dim = dim; a.k_steps = k_steps;
-  a.eta = eta; a.sqrt_eta = sqrt_eta; a.noise_coef = noise_coef;
-  a.table = reinterpret_cast<const float4*>(coef_table);
-  a.noise = noise; a.clamp_on = clamp_on; a.cmin = cmin; a.cmax = cmax;
-  a.thin = thin; a.n_kept = k_steps / thin; a.traj = traj;
-  a.mean = e.dev0; a.prec = e.dev1;
-  a.prec_image = reinterpret_cast<const char*>(e.aux);  // (the resident kernels up to seven tiles do not read it)
-  a.key = RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)};
-  a.step0 = offset;
+  fill_langevin(a, q);
+  a.mean = q.e.dev0; a.prec = q.e.dev1;
+  a.prec_image = reinterpret_cast<const char*>(q.e.aux);  // (the resident kernels up to seven tiles do not read it)
   a.energy_out = nullptr; a.grad_out = nullptr;
   a.diag = diag::DiagArgs{nullptr, 0, 0, 0};
-  if (diag_partials) {
-    if (!gauss_big_diag_plan(n_chains, dim, a.diag)) return fail(EBM_EDIM, "ebm_langevin_chain_f32: no records layout for dim %d", dim);
-    a.diag.partials = diag_partials;
+  if (q.diag_partials) {
+    if (!gauss_big_diag_plan(q.n_chains, dim, a.diag)) return fail(EBM_EDIM, "ebm_langevin_chain_f32: no records layout for dim %d", dim);
+    a.diag.partials = q.diag_partials;
   }
   return dispatch_big(a, dim, st);
 }

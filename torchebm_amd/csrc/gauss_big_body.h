@@ -32,8 +32,7 @@
 // (LDS-direct buffer loads of the fp32 slab would move the split to the readers: 4x the split work), and the normals behind the
 // MFMAs as in gauss_mfma.hip's FAST body (16 OT more registers).
 #pragma once
-#include "ebm_common.h"
-#include "diag.h"
+#include "chain_launch.h"
 #include "gauss_bf16x3.h"
 #include "mlp_b16.h"  // EBM_BLOCK_CUT
 

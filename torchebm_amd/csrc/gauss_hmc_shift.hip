@@ -11,8 +11,6 @@ namespace ebm {
 
 #ifndef EBM_SHIFT_DIAG
 bool gauss_hmc_shift_supported(int32_t dim) { return dim >= 17 && (dim % 4) != 0 && dim + ((dim & 1) ? 3 : 2) <= 160; }
-#else
-bool gauss_hmc_shift_supported(int32_t dim);
 #endif
 
 namespace {
@@ -45,18 +43,15 @@ int launch_hmc_chain_gauss_shift_diag(
 #else
 int launch_hmc_chain_gauss_shift(
 #endif
-    const ebm_energy_t& e, float* x, int64_t n_chains, int32_t dim, int32_t n_mh, int32_t n_leapfrog, float eps,
-    const float* eps_table, int32_t mass_kind, double mass_scalar, const float* mass_diag, int32_t thin, float* traj,
-    uint8_t* accept_mask, uint32_t* accept_count, const float* p_noise, const float* u, uint64_t seed, uint64_t offset,
-    float* diag_partials, hipStream_t st) {
-  if (!gauss_hmc_shift_supported(dim) || (diag_partials != nullptr) != kRecords)
+    const HmcChainReq& q, hipStream_t st) {
+  const int32_t dim = q.dim;
+  if (!gauss_hmc_shift_supported(dim) || (q.diag_partials != nullptr) != kRecords)
     return fail(EBM_EDIM, "ebm_hmc_chain_f32: no shifted-row form for a Gaussian of dim %d", dim);
-  GaussHmcArgs a = matrix_hmc_args(e, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar, mass_diag, thin,
-                                   traj, accept_mask, accept_count, p_noise, u, seed, offset);
+  GaussHmcArgs a = matrix_hmc_args(q);
   a.sh_classes = (dim & 1) ? 4 : 2;
-  if (diag_partials) {
-    diag::plan_classes(n_chains, dim, a.diag);
-    a.diag.partials = diag_partials;
+  if (q.diag_partials) {
+    diag::plan_classes(q.n_chains, dim, a.diag);
+    a.diag.partials = q.diag_partials;
   }
   return a.mass_diag ? launch_shift_nt<true>(a, st) : launch_shift_nt<false>(a, st);
 }

@@ -17,12 +17,9 @@ bool gauss_hmc_stream_supported(const ebm_energy_t& e, int32_t dim) {
          (reinterpret_cast<uintptr_t>(e.aux) & 15) == 0;
 }
 
-int launch_hmc_chain_gauss_stream(const ebm_energy_t& e, float* x, int64_t n_chains, int32_t dim, int32_t n_mh, int32_t n_leapfrog,
-                                  float eps, const float* eps_table, int32_t mass_kind, double mass_scalar, const float* mass_diag,
-                                  int32_t thin, float* traj, uint8_t* accept_mask, uint32_t* accept_count, const float* p_noise,
-                                  const float* u, uint64_t seed, uint64_t offset, hipStream_t st) {
-  const GaussHmcArgs a = matrix_hmc_args(e, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar, mass_diag,
-                                         thin, traj, accept_mask, accept_count, p_noise, u, seed, offset);
+int launch_hmc_chain_gauss_stream(const HmcChainReq& q, hipStream_t st) {
+  const int32_t dim = q.dim;
+  const GaussHmcArgs a = matrix_hmc_args(q);
   const int nt = (dim + 31) / 32;
   if (a.mass_diag) return nt == 6 ? launch_stream<6, true>(a, st) : (nt == 7 ? launch_stream<7, true>(a, st) : launch_stream<8, true>(a, st));
   return nt == 6 ? launch_stream<6, false>(a, st) : (nt == 7 ? launch_stream<7, false>(a, st) : launch_stream<8, false>(a, st));

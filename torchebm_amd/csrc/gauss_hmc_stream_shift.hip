@@ -16,8 +16,6 @@ size_t gauss_prec_image_class_bytes(int32_t dim);
 bool gauss_hmc_stream_shift_supported(const ebm_energy_t& e, int32_t dim) {
   return e.kind == EBM_ENERGY_GAUSSIAN && gauss_stream_shift_dim(dim) && e.aux != nullptr && (reinterpret_cast<uintptr_t>(e.aux) & 15) == 0;
 }
-#else
-bool gauss_hmc_stream_shift_supported(const ebm_energy_t& e, int32_t dim);
 #endif
 
 namespace {
@@ -37,19 +35,16 @@ int launch_hmc_chain_gauss_stream_shift_diag(
 #else
 int launch_hmc_chain_gauss_stream_shift(
 #endif
-    const ebm_energy_t& e, float* x, int64_t n_chains, int32_t dim, int32_t n_mh, int32_t n_leapfrog, float eps,
-    const float* eps_table, int32_t mass_kind, double mass_scalar, const float* mass_diag, int32_t thin, float* traj,
-    uint8_t* accept_mask, uint32_t* accept_count, const float* p_noise, const float* u, uint64_t seed, uint64_t offset,
-    float* diag_partials, hipStream_t st) {
-  if (!gauss_hmc_stream_shift_supported(e, dim) || (diag_partials != nullptr) != kRecords)
+    const HmcChainReq& q, hipStream_t st) {
+  const int32_t dim = q.dim;
+  if (!gauss_hmc_stream_shift_supported(q.e, dim) || (q.diag_partials != nullptr) != kRecords)
     return fail(EBM_EDIM, "ebm_hmc_chain_f32: no streamed shifted-row form for a Gaussian of dim %d", dim);
-  GaussHmcArgs a = matrix_hmc_args(e, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar, mass_diag, thin,
-                                   traj, accept_mask, accept_count, p_noise, u, seed, offset);
+  GaussHmcArgs a = matrix_hmc_args(q);
   a.sh_classes = (dim & 1) ? 4 : 2;
   a.sh_image_stride = (int64_t)gauss_prec_image_class_bytes(dim);
-  if (diag_partials) {
-    diag::plan_classes(n_chains, dim, a.diag);
-    a.diag.partials = diag_partials;
+  if (q.diag_partials) {
+    diag::plan_classes(q.n_chains, dim, a.diag);
+    a.diag.partials = q.diag_partials;
   }
   const int nt = (dim + ((dim & 1) ? 3 : 2) + 31) / 32;
   if (a.mass_diag) return nt == 6 ? launch_stream_shift<6, true>(a, st) : (nt == 7 ? launch_stream_shift<7, true>(a, st) : launch_stream_shift<8, true>(a, st));

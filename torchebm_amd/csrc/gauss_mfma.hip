@@ -115,23 +115,16 @@ int32_t gauss_pack_factor(int32_t dim, int64_t n_chains) {
   return 0;
 }
 
-int launch_langevin_chain_gauss_mfma(const ebm_energy_t& e, float* x, int64_t n_chains, int32_t dim, int32_t k_steps,
-                                     float eta, float sqrt_eta, float noise_coef, const float* coef_table,
-                                     int clamp_on, float cmin, float cmax, int32_t thin, float* traj,
-                                     const float* noise, uint64_t seed, uint64_t offset, hipStream_t st) {
+int launch_langevin_chain_gauss_mfma(const LangevinChainReq& q, hipStream_t st) {
   GaussArgs a{};
+  fill_langevin(a, q);
   // (dims 132 .. 160: FIVE tiles -- the three splits of Ps are 150 KB, the last width whose precision matrix stays resident in LDS)
-  const int32_t pack = gauss_lds5_supported(dim) ? 1 : gauss_pack_factor(dim, n_chains);
-  if (pack < 1) return fail(EBM_EDIM, "ebm_langevin_chain_f32: no matrix-layout form for a Gaussian of dim %d over %lld chains", dim, (long long)n_chains);
-  a.sub_dim = dim; a.pack = pack;
-  n_chains /= pack; dim *= pack;  // the packed geometry from here on
-  a.x = x; a.n_chains = n_chains; a.dim = dim; a.k_steps = k_steps;
-  a.eta = eta; a.sqrt_eta = sqrt_eta; a.noise_coef = noise_coef;
-  a.table = reinterpret_cast<const float4*>(coef_table);
-  a.clamp_on = clamp_on; a.cmin = cmin; a.cmax = cmax;
-  a.thin = thin; a.n_kept = k_steps / thin; a.traj = traj; a.noise = noise;
-  a.key = RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)};
-  a.step0 = offset; a.mean = e.dev0; a.prec = e.dev1;
+  const int32_t pack = gauss_lds5_supported(q.dim) ? 1 : gauss_pack_factor(q.dim, q.n_chains);
+  if (pack < 1) return fail(EBM_EDIM, "ebm_langevin_chain_f32: no matrix-layout form for a Gaussian of dim %d over %lld chains", q.dim, (long long)q.n_chains);
+  a.sub_dim = q.dim; a.pack = pack;
+  a.n_chains = q.n_chains / pack; a.dim = q.dim * pack;  // the packed geometry from here on
+  const int32_t dim = a.dim;
+  a.mean = q.e.dev0; a.prec = q.e.dev1;
   a.gm = gmm3::Params{nullptr, nullptr, 0, dim, 0.0f, 0.0f};
   a.diag = diag::DiagArgs{nullptr, 0, 0, 0}; a.diag_offset_floats = 0;
   // the last 16 coordinates of the last tile all padding: that K-block is left out (EBM_GAUSS_NOTRIM=1: the A/B switch)
@@ -184,18 +177,12 @@ int launch_gmm_langevin_nt(const GaussArgs& a, hipStream_t st) {
 }
 }  // namespace
 
-int launch_langevin_chain_gmm_mfma(const ebm_energy_t& e, float* x, int64_t n_chains, int32_t dim, int32_t k_steps,
-                                   float eta, float sqrt_eta, float noise_coef, const float* coef_table,
-                                   int clamp_on, float cmin, float cmax, int32_t thin, float* traj,
-                                   const float* noise, uint64_t seed, uint64_t offset, hipStream_t st) {
+int launch_langevin_chain_gmm_mfma(const LangevinChainReq& q, hipStream_t st) {
+  const ebm_energy_t& e = q.e;
+  const int32_t dim = q.dim;
   GaussArgs a{};
-  a.x = x; a.n_chains = n_chains; a.dim = dim; a.k_steps = k_steps;
-  a.eta = eta; a.sqrt_eta = sqrt_eta; a.noise_coef = noise_coef;
-  a.table = reinterpret_cast<const float4*>(coef_table);
-  a.clamp_on = clamp_on; a.cmin = cmin; a.cmax = cmax;
-  a.thin = thin; a.n_kept = k_steps / thin; a.traj = traj; a.noise = noise;
-  a.key = RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)};
-  a.step0 = offset; a.mean = nullptr; a.prec = nullptr;
+  fill_langevin(a, q);
+  a.mean = nullptr; a.prec = nullptr;
   a.sub_dim = dim; a.pack = 1;  // (mixtures do not pack)
   a.gm = gmm3::Params{e.dev0, e.dev1, e.n_comp, dim, e.s[0], e.s[1]};
   a.diag = diag::DiagArgs{nullptr, 0, 0, 0}; a.diag_offset_floats = 0;
@@ -212,22 +199,6 @@ int launch_langevin_chain_gmm_mfma(const ebm_energy_t& e, float* x, int64_t n_ch
 // wave of 32 chains from the C/D registers (round 3; rounds 1-2 went through an LDS tile of the workgroup's chains, which did
 // not fit beyond dim 96: a call WITH records then ran on another kernel family than the same call without).
 // ---------------------------------------------------------------------------------
-bool gauss_res_shift_supported(const ebm_energy_t& e, int32_t dim);  // gauss_res_shift.hip: widths off multiples of 4 up to 254, per-class images
-int launch_langevin_chain_gauss_res_shift(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, float, float, float,
-                                          const float*, int, float, float, int32_t, float*, const float*, uint64_t, uint64_t, float*, hipStream_t);
-bool gmm_wide_supported(int32_t dim, int32_t n_comp);        // gmm_wide.hip: mixtures at 132 .. 256 dims (five to eight tiles)
-bool gmm_wide_shift_supported(int32_t dim, int32_t n_comp);  // gmm_wide_shift.hip: ... and the widths off multiples of 4 between 126 and 254
-int launch_langevin_chain_gmm_wide(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, float, float, float,
-                                   const float*, int, float, float, int32_t, float*, const float*, uint64_t, uint64_t, float*, hipStream_t);
-int launch_langevin_chain_gmm_wide_shift(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, float, float, float,
-                                         const float*, int, float, float, int32_t, float*, const float*, uint64_t, uint64_t, float*, hipStream_t);
-bool gmm_shift_supported(int32_t dim, int32_t n_comp);  // gmm_shift.hip
-int launch_langevin_chain_gmm_shift(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, float, float, float,
-                                    const float*, int, float, float, int32_t, float*, const float*, uint64_t, uint64_t, float*, hipStream_t);
-bool gauss_shift_supported(int32_t dim);  // gauss_shift.hip
-int launch_langevin_chain_gauss_shift(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, float, float, float,
-                                      const float*, int, float, float, int32_t, float*, const float*, uint64_t, uint64_t, float*, hipStream_t);
-
 bool matrix_langevin_diag_plan(const ebm_energy_t& e, int64_t n_chains, int32_t dim, diag::DiagArgs& d) {
   // widths off multiples of 4 from 21: shifted rows, the records of their alignment classes interleaved
   static const bool no_shift = ab_switch("EBM_GAUSS_NOSHIFT");
@@ -270,40 +241,28 @@ int launch_matrix_diag_nt(GaussArgs& a, bool mixture, hipStream_t st) {
 }
 }  // namespace
 
-int launch_langevin_chain_matrix_diag(const ebm_energy_t& e, float* x, int64_t n_chains, int32_t dim, int32_t k_steps,
-                                      float eta, float sqrt_eta, float noise_coef, const float* coef_table,
-                                      int clamp_on, float cmin, float cmax, int32_t thin, float* traj,
-                                      const float* noise, uint64_t seed, uint64_t offset, float* diag_partials, hipStream_t st) {
+int launch_langevin_chain_matrix_diag(const LangevinChainReq& q, hipStream_t st) {
+  const ebm_energy_t& e = q.e;
   GaussArgs a{};
-  if (!matrix_langevin_diag_plan(e, n_chains, dim, a.diag))
-    return fail(EBM_EDIM, "ebm_langevin_chain_f32: no matrix-layout diagnostics records for this energy / dim %d", dim);
+  if (!matrix_langevin_diag_plan(e, q.n_chains, q.dim, a.diag))
+    return fail(EBM_EDIM, "ebm_langevin_chain_f32: no matrix-layout diagnostics records for this energy / dim %d", q.dim);
   const bool mixture = e.kind == EBM_ENERGY_GMM;
-  if (mixture && (gmm_wide_supported(dim, e.n_comp) || gmm_wide_shift_supported(dim, e.n_comp)))  // five to eight tiles
-    return (gmm_wide_supported(dim, e.n_comp) ? launch_langevin_chain_gmm_wide : launch_langevin_chain_gmm_wide_shift)(
-        e, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef, coef_table, clamp_on, cmin, cmax, thin, traj, noise, seed, offset,
-        diag_partials, st);
+  if (mixture && (gmm_wide_supported(q.dim, e.n_comp) || gmm_wide_shift_supported(q.dim, e.n_comp)))  // five to eight tiles
+    return gmm_wide_supported(q.dim, e.n_comp) ? launch_langevin_chain_gmm_wide(q, st) : launch_langevin_chain_gmm_wide_shift(q, st);
   if (a.diag.E < 0 && mixture)  // interleaved classes: the shifted-row kernels
-    return launch_langevin_chain_gmm_shift(e, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef, coef_table, clamp_on, cmin, cmax,
-                                           thin, traj, noise, seed, offset, diag_partials, st);
-  if (a.diag.E < 0 && gauss_res_shift_supported(e, dim))
-    return launch_langevin_chain_gauss_res_shift(e, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef, coef_table, clamp_on, cmin, cmax,
-                                                 thin, traj, noise, seed, offset, diag_partials, st);
+    return launch_langevin_chain_gmm_shift(q, st);
+  if (a.diag.E < 0 && gauss_res_shift_supported(e, q.dim))
+    return launch_langevin_chain_gauss_res_shift(q, st);
   if (a.diag.E < 0)
-    return launch_langevin_chain_gauss_shift(e, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef, coef_table, clamp_on, cmin, cmax,
-                                             thin, traj, noise, seed, offset, diag_partials, st);
-  const int32_t pack = mixture ? 1 : gauss_pack_factor(dim, n_chains);
-  a.sub_dim = dim; a.pack = pack;
-  n_chains /= pack; dim *= pack;  // the packed geometry from here on
-  a.x = x; a.n_chains = n_chains; a.dim = dim; a.k_steps = k_steps;
-  a.eta = eta; a.sqrt_eta = sqrt_eta; a.noise_coef = noise_coef;
-  a.table = reinterpret_cast<const float4*>(coef_table);
-  a.clamp_on = clamp_on; a.cmin = cmin; a.cmax = cmax;
-  a.thin = thin; a.n_kept = k_steps / thin; a.traj = traj; a.noise = noise;
-  a.key = RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)};
-  a.step0 = offset;
+    return launch_langevin_chain_gauss_shift(q, st);
+  fill_langevin(a, q);
+  const int32_t pack = mixture ? 1 : gauss_pack_factor(q.dim, q.n_chains);
+  a.sub_dim = q.dim; a.pack = pack;
+  a.n_chains = q.n_chains / pack; a.dim = q.dim * pack;  // the packed geometry from here on
+  const int32_t dim = a.dim;
   a.mean = mixture ? nullptr : e.dev0; a.prec = mixture ? nullptr : e.dev1;
   a.gm = mixture ? gmm3::Params{e.dev0, e.dev1, e.n_comp, dim, e.s[0], e.s[1]} : gmm3::Params{nullptr, nullptr, 0, dim, 0.0f, 0.0f};
-  a.diag.partials = diag_partials;
+  a.diag.partials = q.diag_partials;
   switch ((dim + 31) / 32) {
     case 1: return launch_matrix_diag_nt<1>(a, mixture, st);
     case 2: return launch_matrix_diag_nt<2>(a, mixture, st);

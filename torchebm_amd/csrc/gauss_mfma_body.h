@@ -1,8 +1,7 @@
 // The matrix-layout Langevin chain body for the dense Gaussian / isotropic mixtures (kernels and launchers: gauss_mfma.hip,
 // gauss_shift.hip).  Split out so that the shifted-row instantiations compile as a translation unit of their own.
 #pragma once
-#include "ebm_common.h"
-#include "diag.h"
+#include "chain_launch.h"
 #include "gauss_bf16x3.h"
 #include "gmm_bf16x3.h"
 

@@ -63,26 +63,19 @@ inline int32_t shift_extent(int32_t dim) { return dim + ((dim & 1) ? 3 : 2); }
 // below 17 the packed rows stay (gauss_pack_factor: the padding of a 32-wide tile outweighs the block-diagonal waste there)
 bool gauss_shift_supported(int32_t dim) { return dim >= 17 && (dim % 4) != 0 && shift_extent(dim) <= 160; }
 
-int launch_langevin_chain_gauss_shift(const ebm_energy_t& e, float* x, int64_t n_chains, int32_t dim, int32_t k_steps,
-                                      float eta, float sqrt_eta, float noise_coef, const float* coef_table,
-                                      int clamp_on, float cmin, float cmax, int32_t thin, float* traj,
-                                      const float* noise, uint64_t seed, uint64_t offset, float* diag_partials, hipStream_t st) {
+int launch_langevin_chain_gauss_shift(const LangevinChainReq& q, hipStream_t st) {
+  const int32_t dim = q.dim;
   if (!gauss_shift_supported(dim)) return fail(EBM_EDIM, "ebm_langevin_chain_f32: no shifted-row form for a Gaussian of dim %d", dim);
   GaussArgs a{};
   a.sub_dim = dim; a.pack = 1;
   a.sh_classes = (dim & 1) ? 4 : 2;
-  a.x = x; a.n_chains = n_chains; a.dim = dim; a.k_steps = k_steps;
-  a.eta = eta; a.sqrt_eta = sqrt_eta; a.noise_coef = noise_coef;
-  a.table = reinterpret_cast<const float4*>(coef_table);
-  a.clamp_on = clamp_on; a.cmin = cmin; a.cmax = cmax;
-  a.thin = thin; a.n_kept = k_steps / thin; a.traj = traj; a.noise = noise;
-  a.key = RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)};
-  a.step0 = offset; a.mean = e.dev0; a.prec = e.dev1;
+  fill_langevin(a, q);
+  a.mean = q.e.dev0; a.prec = q.e.dev1;
   a.gm = gmm3::Params{nullptr, nullptr, 0, dim, 0.0f, 0.0f};
   a.diag = diag::DiagArgs{nullptr, 0, 0, 0}; a.diag_offset_floats = 0;
-  if (diag_partials) {  // one record per wave, the classes interleaved (diag.h plan_classes)
-    diag::plan_classes(n_chains, dim, a.diag);
-    a.diag.partials = diag_partials;
+  if (q.diag_partials) {  // one record per wave, the classes interleaved (diag.h plan_classes)
+    diag::plan_classes(q.n_chains, dim, a.diag);
+    a.diag.partials = q.diag_partials;
   }
   const int ext = shift_extent(dim), nt = (ext + 31) / 32;
   const bool trim = 32 * nt - ext >= 16;

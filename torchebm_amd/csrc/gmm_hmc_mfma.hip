@@ -33,13 +33,8 @@ int launch_gmm_dim(const GaussHmcArgs& a, hipStream_t st) {
 }
 }  // namespace
 
-int launch_hmc_chain_gmm_mfma(const ebm_energy_t& e, float* x, int64_t n_chains, int32_t dim, int32_t n_mh,
-                              int32_t n_leapfrog, float eps, const float* eps_table, int32_t mass_kind,
-                              double mass_scalar, const float* mass_diag, int32_t thin, float* traj, uint8_t* accept_mask,
-                              uint32_t* accept_count, const float* p_noise, const float* u, uint64_t seed,
-                              uint64_t offset, hipStream_t st) {
-  const GaussHmcArgs a = matrix_hmc_args(e, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar, mass_diag,
-                                         thin, traj, accept_mask, accept_count, p_noise, u, seed, offset);
+int launch_hmc_chain_gmm_mfma(const HmcChainReq& q, hipStream_t st) {
+  const GaussHmcArgs a = matrix_hmc_args(q);
   return a.mass_diag ? launch_gmm_dim<true>(a, st) : launch_gmm_dim<false>(a, st);
 }
 

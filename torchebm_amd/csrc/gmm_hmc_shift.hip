@@ -22,8 +22,6 @@ bool gmm_hmc_shift_supported(int32_t dim, int32_t n_comp, int32_t mass_kind, boo
   const int max_ext = (records || mass_kind == EBM_MASS_DIAG) ? 96 : 128;
   return dim >= (n_comp > 8 ? 9 : 17) && (dim % 4) != 0 && shift_extent(dim) <= max_ext && n_comp >= 1 && n_comp <= 32;
 }
-#else
-bool gmm_hmc_shift_supported(int32_t dim, int32_t n_comp, int32_t mass_kind, bool records);
 #endif
 
 namespace {
@@ -51,18 +49,16 @@ int launch_hmc_chain_gmm_shift_diag(
 #else
 int launch_hmc_chain_gmm_shift(
 #endif
-    const ebm_energy_t& e, float* x, int64_t n_chains, int32_t dim, int32_t n_mh, int32_t n_leapfrog, float eps,
-    const float* eps_table, int32_t mass_kind, double mass_scalar, const float* mass_diag, int32_t thin, float* traj,
-    uint8_t* accept_mask, uint32_t* accept_count, const float* p_noise, const float* u, uint64_t seed, uint64_t offset,
-    float* diag_partials, hipStream_t st) {
-  if (!gmm_hmc_shift_supported(dim, e.n_comp, mass_kind, kRecords) || (diag_partials != nullptr) != kRecords)
+    const HmcChainReq& q, hipStream_t st) {
+  const ebm_energy_t& e = q.e;
+  const int32_t dim = q.dim;
+  if (!gmm_hmc_shift_supported(dim, e.n_comp, q.mass_kind, kRecords) || (q.diag_partials != nullptr) != kRecords)
     return fail(EBM_EDIM, "ebm_hmc_chain_f32: no shifted-row form for a mixture of dim %d", dim);
-  GaussHmcArgs a = matrix_hmc_args(e, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar, mass_diag, thin,
-                                   traj, accept_mask, accept_count, p_noise, u, seed, offset);
+  GaussHmcArgs a = matrix_hmc_args(q);
   a.sh_classes = (dim & 1) ? 4 : 2;
-  if (diag_partials) {
-    diag::plan_classes(n_chains, dim, a.diag);
-    a.diag.partials = diag_partials;
+  if (q.diag_partials) {
+    diag::plan_classes(q.n_chains, dim, a.diag);
+    a.diag.partials = q.diag_partials;
   }
   return a.mass_diag ? launch_dim<true>(a, st) : launch_dim<false>(a, st);
 }

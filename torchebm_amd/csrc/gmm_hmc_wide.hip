@@ -66,14 +66,12 @@ bool gmm_hmc_wide_supported(int32_t dim, int32_t n_comp, int32_t mass_kind) {
 }
 int launch_hmc_chain_gmm_wide(
 #endif
-    const ebm_energy_t& e, float* x, int64_t n_chains, int32_t dim, int32_t n_mh, int32_t n_leapfrog, float eps,
-    const float* eps_table, int32_t mass_kind, double mass_scalar, const float* mass_diag, int32_t thin, float* traj,
-    uint8_t* accept_mask, uint32_t* accept_count, const float* p_noise, const float* u, uint64_t seed, uint64_t offset,
-    hipStream_t st) {
-  if (mass_kind == EBM_MASS_DIAG || extent(dim) <= 128 || !tiles_pay(extent(dim), e.n_comp, dim) || ((dim % 4) != 0) != kSh)
+    const HmcChainReq& q, hipStream_t st) {
+  const ebm_energy_t& e = q.e;
+  const int32_t dim = q.dim;
+  if (q.mass_kind == EBM_MASS_DIAG || extent(dim) <= 128 || !tiles_pay(extent(dim), e.n_comp, dim) || ((dim % 4) != 0) != kSh)
     return fail(EBM_EDIM, "ebm_hmc_chain_f32: no wide matrix-layout form for a mixture of dim %d", dim);
-  GaussHmcArgs a = matrix_hmc_args(e, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar, mass_diag, thin,
-                                   traj, accept_mask, accept_count, p_noise, u, seed, offset);
+  GaussHmcArgs a = matrix_hmc_args(q);
   a.sh_classes = kSh ? ((dim & 1) ? 4 : 2) : 1;
   switch ((extent(dim) + 31) / 32) {
     case 5: return launch_nt<5>(a, st);

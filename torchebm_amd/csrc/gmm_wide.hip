@@ -57,25 +57,20 @@ int launch_langevin_chain_gmm_wide_shift(
 bool gmm_wide_supported(int32_t dim, int32_t n_comp) { return (dim % 4) == 0 && dim > 128 && dim <= 256 && n_comp >= 1 && n_comp <= 32; }
 int launch_langevin_chain_gmm_wide(
 #endif
-    const ebm_energy_t& e, float* x, int64_t n_chains, int32_t dim, int32_t k_steps, float eta, float sqrt_eta, float noise_coef,
-    const float* coef_table, int clamp_on, float cmin, float cmax, int32_t thin, float* traj, const float* noise, uint64_t seed,
-    uint64_t offset, float* diag_partials, hipStream_t st) {
+    const LangevinChainReq& q, hipStream_t st) {
+  const ebm_energy_t& e = q.e;
+  const int32_t dim = q.dim;
   GaussArgs a{};
   a.sub_dim = dim; a.pack = 1;
   a.sh_classes = kSh ? ((dim & 1) ? 4 : 2) : 1;
-  a.x = x; a.n_chains = n_chains; a.dim = dim; a.k_steps = k_steps;
-  a.eta = eta; a.sqrt_eta = sqrt_eta; a.noise_coef = noise_coef;
-  a.table = reinterpret_cast<const float4*>(coef_table);
-  a.clamp_on = clamp_on; a.cmin = cmin; a.cmax = cmax;
-  a.thin = thin; a.n_kept = k_steps / thin; a.traj = traj; a.noise = noise;
-  a.key = RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)};
-  a.step0 = offset; a.mean = nullptr; a.prec = nullptr;
+  fill_langevin(a, q);
+  a.mean = nullptr; a.prec = nullptr;
   a.gm = gmm3::Params{e.dev0, e.dev1, e.n_comp, dim, e.s[0], e.s[1]};
   a.diag = diag::DiagArgs{nullptr, 0, 0, 0}; a.diag_offset_floats = 0;
-  if (diag_partials) {  // one record per wave of 32 chains (shifted rows: the classes interleaved, diag.h plan_classes)
-    if (kSh) diag::plan_classes(n_chains, dim, a.diag);
-    else diag::plan(n_chains, dim, 32 * (int64_t)dim, a.diag);
-    a.diag.partials = diag_partials;
+  if (q.diag_partials) {  // one record per wave of 32 chains (shifted rows: the classes interleaved, diag.h plan_classes)
+    if (kSh) diag::plan_classes(q.n_chains, dim, a.diag);
+    else diag::plan(q.n_chains, dim, 32 * (int64_t)dim, a.diag);
+    a.diag.partials = q.diag_partials;
   }
   switch ((extent(dim) + 31) / 32) {
     case 5: return launch_wide_nt<5>(a, st);

@@ -4,6 +4,7 @@
 // torchebm/integrators/leapfrog.py:156-185, torchebm/core/base_integrator.py:875-889.
 #include <cstdlib>
 
+#include "chain_launch.h"
 #include "hmc_kernel.h"
 
 namespace ebm {
@@ -31,50 +32,6 @@ bool hmc_gmm32_applies(const ebm_energy_t&, const rows::Geometry&, int32_t mass_
 void launch_gmm32(dim3, hipStream_t, HmcArgs);
 }  // namespace hmc
 using hmc::HmcArgs;
-
-bool gauss_hmc_mfma_supported(int32_t dim, int32_t mass_kind);
-bool gauss_hmc_shift_supported(int32_t dim);  // gauss_hmc_shift.hip: widths off multiples of 4, 17 .. 158, on shifted rows
-int launch_hmc_chain_gauss_shift(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, int32_t, float, const float*, int32_t, double,
-                                 const float*, int32_t, float*, uint8_t*, uint32_t*, const float*, const float*, uint64_t, uint64_t,
-                                 float*, hipStream_t);
-int launch_hmc_chain_gauss_shift_diag(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, int32_t, float, const float*, int32_t,
-                                      double, const float*, int32_t, float*, uint8_t*, uint32_t*, const float*, const float*, uint64_t,
-                                      uint64_t, float*, hipStream_t);
-bool gauss_hmc_stream_supported(const ebm_energy_t& e, int32_t dim);  // gauss_hmc_stream.hip: dims 164 .. 256 with the pre-split image
-bool gauss_hmc_stream_shift_supported(const ebm_energy_t& e, int32_t dim);  // gauss_hmc_stream_shift.hip: ... and the widths between them
-int launch_hmc_chain_gauss_stream_shift(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, int32_t, float, const float*, int32_t,
-                                        double, const float*, int32_t, float*, uint8_t*, uint32_t*, const float*, const float*, uint64_t,
-                                        uint64_t, float*, hipStream_t);
-int launch_hmc_chain_gauss_stream_shift_diag(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, int32_t, float, const float*, int32_t,
-                                             double, const float*, int32_t, float*, uint8_t*, uint32_t*, const float*, const float*,
-                                             uint64_t, uint64_t, float*, hipStream_t);
-int launch_hmc_chain_gauss_stream(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, int32_t, float, const float*, int32_t, double,
-                                  const float*, int32_t, float*, uint8_t*, uint32_t*, const float*, const float*, uint64_t, uint64_t, hipStream_t);
-bool gmm_hmc_mfma_supported(int32_t dim, int32_t n_comp, int32_t mass_kind);
-bool gmm_hmc_shift_supported(int32_t dim, int32_t n_comp, int32_t mass_kind, bool records);  // gmm_hmc_shift.hip
-int launch_hmc_chain_gmm_shift(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, int32_t, float, const float*, int32_t, double,
-                               const float*, int32_t, float*, uint8_t*, uint32_t*, const float*, const float*, uint64_t, uint64_t,
-                               float*, hipStream_t);
-int launch_hmc_chain_gmm_shift_diag(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, int32_t, float, const float*, int32_t,
-                                    double, const float*, int32_t, float*, uint8_t*, uint32_t*, const float*, const float*, uint64_t,
-                                    uint64_t, float*, hipStream_t);
-bool gmm_hmc_wide_supported(int32_t dim, int32_t n_comp, int32_t mass_kind);        // gmm_hmc_wide.hip: mixtures at 132 .. 224 dims
-bool gmm_hmc_wide_shift_supported(int32_t dim, int32_t n_comp, int32_t mass_kind);  // gmm_hmc_wide_shift.hip: ... and the widths between
-int launch_hmc_chain_gmm_wide(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, int32_t, float, const float*, int32_t, double,
-                              const float*, int32_t, float*, uint8_t*, uint32_t*, const float*, const float*, uint64_t, uint64_t, hipStream_t);
-int launch_hmc_chain_gmm_wide_shift(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, int32_t, float, const float*, int32_t, double,
-                                    const float*, int32_t, float*, uint8_t*, uint32_t*, const float*, const float*, uint64_t, uint64_t,
-                                    hipStream_t);
-bool matrix_hmc_diag_plan(const ebm_energy_t&, int64_t, int32_t, diag::DiagArgs&);
-int launch_hmc_chain_matrix_diag(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, int32_t, float, const float*,
-                                 int32_t, double, const float*, int32_t, float*, uint8_t*, uint32_t*, const float*, const float*,
-                                 uint64_t, uint64_t, float*, hipStream_t);
-int launch_hmc_chain_gmm_mfma(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, int32_t, float, const float*,
-                              int32_t, double, const float*, int32_t, float*, uint8_t*, uint32_t*, const float*, const float*,
-                              uint64_t, uint64_t, hipStream_t);
-int launch_hmc_chain_gauss_mfma(const ebm_energy_t&, float*, int64_t, int32_t, int32_t, int32_t, float, const float*,
-                                int32_t, double, const float*, int32_t, float*, uint8_t*, uint32_t*, const float*, const float*,
-                                uint64_t, uint64_t, hipStream_t);
 
 // Lane geometry of the transition kernel for this energy / row width (shared by the launcher and the
 // diagnostics layout query, which must agree).
@@ -128,91 +85,59 @@ bool hmc_diag_plan(const ebm_energy_t& e, int64_t n_chains, int32_t dim, diag::D
   return diag::plan(n_chains, dim, (int64_t)(kBlock / geo.G) * dim, d);
 }
 
-int launch_hmc_chain(const ebm_energy_t& e, float* x, int64_t n_chains, int32_t dim, int32_t n_mh,
-                     int32_t n_leapfrog, float eps, const float* eps_table, int32_t mass_kind,
-                     double mass_scalar, const float* mass_diag, int32_t thin, float* traj,
-                     uint8_t* accept_mask, uint32_t* accept_count, const float* p_noise,
-                     const float* u, uint64_t seed, uint64_t offset, float* diag_partials, hipStream_t st) {
-  if (diag_partials) {
-    diag::DiagArgs dm;
-    if (hmc_matrix_records(e, n_chains, dim, dm) && dm.E < 0 && gauss_hmc_stream_shift_supported(e, dim))
-      return launch_hmc_chain_gauss_stream_shift_diag(e, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar,
-                                                      mass_diag, thin, traj, accept_mask, accept_count, p_noise, u, seed, offset,
-                                                      diag_partials, st);
-    if (hmc_matrix_records(e, n_chains, dim, dm) && dm.E < 0 && e.kind == EBM_ENERGY_GMM)
-      return launch_hmc_chain_gmm_shift_diag(e, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar, mass_diag,
-                                             thin, traj, accept_mask, accept_count, p_noise, u, seed, offset, diag_partials, st);
-    if (hmc_matrix_records(e, n_chains, dim, dm) && dm.E < 0)
-      return launch_hmc_chain_gauss_shift_diag(e, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar, mass_diag,
-                                               thin, traj, accept_mask, accept_count, p_noise, u, seed, offset, diag_partials, st);
-    if (hmc_matrix_records(e, n_chains, dim, dm))
-      return launch_hmc_chain_matrix_diag(e, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar, mass_diag,
-                                          thin, traj, accept_mask, accept_count, p_noise, u, seed, offset, diag_partials, st);
+int launch_hmc_chain(const HmcChainReq& q, hipStream_t st) {
+  const ebm_energy_t& e = q.e;
+  const int32_t dim = q.dim, mass_kind = q.mass_kind;
+  diag::DiagArgs dm;
+  if (q.diag_partials && hmc_matrix_records(e, q.n_chains, dim, dm)) {
+    if (dm.E < 0 && gauss_hmc_stream_shift_supported(e, dim)) return launch_hmc_chain_gauss_stream_shift_diag(q, st);
+    if (dm.E < 0 && e.kind == EBM_ENERGY_GMM) return launch_hmc_chain_gmm_shift_diag(q, st);
+    if (dm.E < 0) return launch_hmc_chain_gauss_shift_diag(q, st);
+    return launch_hmc_chain_matrix_diag(q, st);
   }
   // (records beyond those shapes: the lane-group kernels)
-  if (!diag_partials && e.kind == EBM_ENERGY_GAUSSIAN && gauss_hmc_shift_supported(dim)) {
+  if (!q.diag_partials && e.kind == EBM_ENERGY_GAUSSIAN && gauss_hmc_shift_supported(dim)) {
     // A/B switch: EBM_GAUSS_NOSHIFT=1 keeps the lane-group kernel for widths off multiples of 4
     static const bool no_shift = ab_switch("EBM_GAUSS_NOSHIFT");
-    if (!no_shift)
-      return launch_hmc_chain_gauss_shift(e, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar, mass_diag,
-                                          thin, traj, accept_mask, accept_count, p_noise, u, seed, offset, nullptr, st);
+    if (!no_shift) return launch_hmc_chain_gauss_shift(q, st);
   }
-  if (!diag_partials && e.kind == EBM_ENERGY_GAUSSIAN && gauss_hmc_mfma_supported(dim, mass_kind)) {
+  if (!q.diag_partials && e.kind == EBM_ENERGY_GAUSSIAN && gauss_hmc_mfma_supported(dim, mass_kind)) {
     // A/B switch for tests and profiling: EBM_GAUSS_ROWS=1 keeps the LDS mat-vec kernel
     static const bool force_rows = ab_switch("EBM_GAUSS_ROWS");
-    if (!force_rows)
-      return launch_hmc_chain_gauss_mfma(e, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar,
-                                         mass_diag, thin, traj, accept_mask, accept_count, p_noise, u, seed, offset, st);
+    if (!force_rows) return launch_hmc_chain_gauss_mfma(q, st);
   }
-  if (!diag_partials && e.kind == EBM_ENERGY_GMM && gmm_hmc_shift_supported(dim, e.n_comp, mass_kind, false)) {
+  if (!q.diag_partials && e.kind == EBM_ENERGY_GMM && gmm_hmc_shift_supported(dim, e.n_comp, mass_kind, false)) {
     static const bool no_shift = ab_switch("EBM_GAUSS_NOSHIFT");
-    if (!no_shift)
-      return launch_hmc_chain_gmm_shift(e, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar, mass_diag,
-                                        thin, traj, accept_mask, accept_count, p_noise, u, seed, offset, nullptr, st);
+    if (!no_shift) return launch_hmc_chain_gmm_shift(q, st);
   }
-  if (!diag_partials && gauss_hmc_stream_shift_supported(e, dim)) {
+  if (!q.diag_partials && gauss_hmc_stream_shift_supported(e, dim)) {
     static const bool no_shift = ab_switch("EBM_GAUSS_NOSHIFT");
-    if (!no_shift)
-      return launch_hmc_chain_gauss_stream_shift(e, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar, mass_diag,
-                                                 thin, traj, accept_mask, accept_count, p_noise, u, seed, offset, nullptr, st);
+    if (!no_shift) return launch_hmc_chain_gauss_stream_shift(q, st);
   }
-  if (!diag_partials && gauss_hmc_stream_supported(e, dim))
-    return launch_hmc_chain_gauss_stream(e, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar, mass_diag, thin,
-                                         traj, accept_mask, accept_count, p_noise, u, seed, offset, st);
+  if (!q.diag_partials && gauss_hmc_stream_supported(e, dim)) return launch_hmc_chain_gauss_stream(q, st);
   // Mixtures of up to 32 components, dims 20 .. 96: the two K x dim passes of the gradient on the bf16 matrix pipe
   // (gauss_hmc_mfma.hip: GmmE).  One shape stays on the lane-group kernel: dim 32 with K <= 8, where one lane per chain
   // with the means as scalar operands (and the active-column body) is faster -- dense means, ms per 10 transitions at
   // L = 20, 2^18 chains (scripts/bench_gmm_dense.py): dim 32: K = 8 0.96 there vs 1.43 here, K = 16 / 32 4.30 / 7.86 vs
   // 1.63 / 2.38; dim 64: K = 8 / 16 / 32 4.20 / 8.71 / 16.0 vs 3.07 / 3.52 / 5.41.
-  if (!diag_partials && e.kind == EBM_ENERGY_GMM && gmm_hmc_mfma_supported(dim, e.n_comp, mass_kind) &&
+  if (!q.diag_partials && e.kind == EBM_ENERGY_GMM && gmm_hmc_mfma_supported(dim, e.n_comp, mass_kind) &&
       !(dim == 32 && e.n_comp <= 8)) {
     // A/B switch for tests and profiling: EBM_GMM_ROWS=1 keeps the lane-group kernels
     static const bool force_rows = ab_switch("EBM_GMM_ROWS");
-    if (!force_rows)
-      return launch_hmc_chain_gmm_mfma(e, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar,
-                                       mass_diag, thin, traj, accept_mask, accept_count, p_noise, u, seed, offset, st);
+    if (!force_rows) return launch_hmc_chain_gmm_mfma(q, st);
   }
   // Mixtures at 129 .. 224 dims (no mass vector, no records): five to seven tiles of the same body, where they beat the lane-group kernels
-  if (!diag_partials && e.kind == EBM_ENERGY_GMM &&
+  if (!q.diag_partials && e.kind == EBM_ENERGY_GMM &&
       (gmm_hmc_wide_supported(dim, e.n_comp, mass_kind) || gmm_hmc_wide_shift_supported(dim, e.n_comp, mass_kind))) {
     static const bool force_rows = ab_switch("EBM_GMM_ROWS");
     if (!force_rows)
-      return (gmm_hmc_wide_supported(dim, e.n_comp, mass_kind) ? launch_hmc_chain_gmm_wide : launch_hmc_chain_gmm_wide_shift)(
-          e, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar, mass_diag, thin, traj, accept_mask, accept_count,
-          p_noise, u, seed, offset, st);
+      return gmm_hmc_wide_supported(dim, e.n_comp, mass_kind) ? launch_hmc_chain_gmm_wide(q, st) : launch_hmc_chain_gmm_wide_shift(q, st);
   }
   Geometry geo;
   if (!hmc_geometry(e, dim, geo)) return fail(EBM_EDIM, "ebm_hmc_chain_f32: dim %d > 1024 is not supported by the fused kernel", dim);
   HmcArgs a{};
-  a.x = x; a.n_chains = n_chains; a.dim = dim; a.n_mh = n_mh; a.n_leapfrog = n_leapfrog;
-  a.eps = eps; a.eps_table = eps_table; a.mass_kind = mass_kind;
-  a.mass_raw = (float)mass_scalar;
-  a.mass_sqrt = (float)sqrt(mass_scalar);
-  a.mass_safe = (float)(mass_scalar < 1e-10 ? 1e-10 : mass_scalar);
-  a.mass_diag = mass_diag; a.thin = thin; a.n_kept = n_mh / thin; a.traj = traj;
-  a.accept_mask = accept_mask; a.accept_count = accept_count; a.p_noise = p_noise; a.u = u;
-  a.key = RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)};
-  a.step0 = offset;
+  fill_hmc(a, q);
+  a.mass_kind = q.mass_kind; a.mass_diag = q.mass_diag;
   size_t smem = 0;
   plan_params(e, dim, geo, a.energy, a.param_floats, smem);
   a.park_offset_floats = (int)(smem / sizeof(float));
@@ -220,22 +145,22 @@ int launch_hmc_chain(const ebm_energy_t& e, float* x, int64_t n_chains, int32_t 
   if (geo.NV >= 4) smem += (size_t)kBlock * geo.NV * 16 * (geo.NV <= 4 ? 3 : 2);
   a.diag = diag::DiagArgs{nullptr, 0, 0, 0};
   a.diag_offset_floats = (int)(smem / sizeof(float));
-  const bool diag_kernel = diag_partials != nullptr;
+  const bool diag_kernel = q.diag_partials != nullptr;
   if (diag_kernel) {
-    if (!diag::plan(n_chains, dim, (int64_t)(kBlock / geo.G) * dim, a.diag))
+    if (!diag::plan(q.n_chains, dim, (int64_t)(kBlock / geo.G) * dim, a.diag))
       return fail(EBM_EDIM, "ebm_hmc_chain_f32: diagnostics records are not available for dim %d", dim);
-    a.diag.partials = diag_partials;
+    a.diag.partials = q.diag_partials;
     // scratch rows, then (narrow rows only: the wide ones reuse the state's parking slot) the tile
     smem += (size_t)(geo.NV >= 4 ? diag::scratch_floats(a.diag.S) : diag::lds_floats(a.diag.E, a.diag.S)) * sizeof(float);
   }
-  const int64_t blocks = blocks_for(n_chains, geo);
+  const int64_t blocks = blocks_for(q.n_chains, geo);
   if (blocks > 0x7fffffffLL) return fail(EBM_EINVAL, "ebm_hmc_chain_f32: too many chains for one launch");
   const dim3 grid((unsigned)blocks);
   // A mixture at dim 32 with K <= 8 and identity mass, one lane per chain: two kernels are launched back to back and each
   // reads the active-column mask itself -- hmc_ring.hip does the work when the means differ inside ONE four-column slot
   // (gmm_single_slot: any slot, not only the first) and returns at once otherwise; hmc_gmm32.hip does it for every other
   // mask and returns at once for a single slot.  (Both index chains with 32 bits: a dim-32 state of 2^32 chains is 512 GiB.)
-  if ((hmc::hmc_slot1_applies(e, geo, mass_kind) || hmc::hmc_gmm32_applies(e, geo, mass_kind)) && n_chains >= (1LL << 32))
+  if ((hmc::hmc_slot1_applies(e, geo, mass_kind) || hmc::hmc_gmm32_applies(e, geo, mass_kind)) && q.n_chains >= (1LL << 32))
     return fail(EBM_EINVAL, "ebm_hmc_chain_f32: more than 2^32 - 1 chains in one launch");
   if (hmc::hmc_slot1_applies(e, geo, mass_kind)) hmc::launch_slot1(grid, st, a);
   if (hmc::hmc_gmm32_applies(e, geo, mass_kind)) {  // (returns at once when the mask names a single slot)
@@ -261,10 +186,9 @@ int launch_hmc_chain(const ebm_energy_t& e, float* x, int64_t n_chains, int32_t 
 }
 
 // ebm_hmc_chain_audit_f32: the literal leapfrog sequence (hmc_kernel.h: leapfrog_literal) -- element-wise energies, dim <= 256
-int launch_hmc_chain_audit(const ebm_energy_t& e, float* x, int64_t n_chains, int32_t dim, int32_t n_mh, int32_t n_leapfrog, float eps,
-                           const float* eps_table, int32_t mass_kind, double mass_scalar, const float* mass_diag, int32_t thin,
-                           float* traj, uint8_t* accept_mask, uint32_t* accept_count, const float* p_noise, const float* u,
-                           uint64_t seed, uint64_t offset, hipStream_t st) {
+int launch_hmc_chain_audit(const HmcChainReq& q, hipStream_t st) {
+  const ebm_energy_t& e = q.e;
+  const int32_t dim = q.dim;
   const char* who = "ebm_hmc_chain_audit_f32";
   if (e.kind != EBM_ENERGY_DOUBLE_WELL && e.kind != EBM_ENERGY_HARMONIC)
     return fail(EBM_EKIND, "%s: the audit form exists for the element-wise energies (double well, harmonic)", who);
@@ -272,21 +196,14 @@ int launch_hmc_chain_audit(const ebm_energy_t& e, float* x, int64_t n_chains, in
   if (!pick_geometry(dim, geo) || geo.NV != 1) return fail(EBM_EDIM, "%s: dim %d > 256", who, dim);
   geo.full = false;
   HmcArgs a{};
-  a.x = x; a.n_chains = n_chains; a.dim = dim; a.n_mh = n_mh; a.n_leapfrog = n_leapfrog;
-  a.eps = eps; a.eps_table = eps_table; a.mass_kind = mass_kind;
-  a.mass_raw = (float)mass_scalar;
-  a.mass_sqrt = (float)sqrt(mass_scalar);
-  a.mass_safe = (float)(mass_scalar < 1e-10 ? 1e-10 : mass_scalar);
-  a.mass_diag = mass_diag; a.thin = thin; a.n_kept = n_mh / thin; a.traj = traj;
-  a.accept_mask = accept_mask; a.accept_count = accept_count; a.p_noise = p_noise; a.u = u;
-  a.key = RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)};
-  a.step0 = offset;
+  fill_hmc(a, q);
+  a.mass_kind = q.mass_kind; a.mass_diag = q.mass_diag;
   size_t smem = 0;
   plan_params(e, dim, geo, a.energy, a.param_floats, smem);
   a.park_offset_floats = (int)(smem / sizeof(float));
   a.diag = diag::DiagArgs{nullptr, 0, 0, 0};
   a.diag_offset_floats = (int)(smem / sizeof(float));
-  const int64_t blocks = blocks_for(n_chains, geo);
+  const int64_t blocks = blocks_for(q.n_chains, geo);
   if (blocks > 0x7fffffffLL) return fail(EBM_EINVAL, "%s: too many chains for one launch", who);
   const dim3 grid((unsigned)blocks);
   if (e.kind == EBM_ENERGY_DOUBLE_WELL) hmc::launch_literal_double_well(geo, grid, smem, st, a);

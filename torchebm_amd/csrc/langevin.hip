@@ -274,27 +274,16 @@ int launch_langevin_step(const float* x, const float* grad, float* out, const fl
   return check_launch("ebm_langevin_step_f32");
 }
 
-int launch_langevin_chain_elem(int kind, float s0, float s1, float* x, int64_t n_chains, int32_t dim,
-                               int32_t k_steps, float eta, float sqrt_eta, float noise_coef,
-                               const float* coef_table, int clamp_on, float cmin, float cmax,
-                               int32_t thin, float* traj, const float* noise, uint64_t seed,
-                               uint64_t offset, int heun, int contracted, hipStream_t st) {
-  ChainArgs a{};
-  a.x = x; a.n_elem = n_chains * (int64_t)dim; a.dim = dim; a.k_steps = k_steps;
-  a.c = StepCoef{eta, sqrt_eta, noise_coef};
-  a.table = reinterpret_cast<const float4*>(coef_table);
-  a.clamp_on = clamp_on; a.cmin = cmin; a.cmax = cmax;
-  a.thin = thin; a.n_kept = k_steps / thin; a.traj = traj; a.noise = noise;
-  a.s0 = s0; a.s1 = s1;
-  a.key = RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)};
-  a.step0 = offset;
+int launch_langevin_chain_elem(const LangevinChainReq& q, hipStream_t st) {
+  ChainArgs a = elem_chain_args(q);
+  a.noise = q.noise;
   a.diag = diag::DiagArgs{nullptr, 0, 0, 0};
   const int64_t n_groups = ceil_div64(a.n_elem, 4);
   const int64_t blocks = ceil_div64(n_groups, kBlock);
   if (blocks > 0x7fffffffLL) return fail(EBM_EINVAL, "state too large for one launch (%lld blocks)", (long long)blocks);
   const dim3 grid((unsigned)blocks), block(kBlock);
-  if (!noise && heun && !traj && !coef_table && !clamp_on) {  // plain Heun chain: the lean loop with a second gradient
-    if (kind == EBM_ENERGY_DOUBLE_WELL)
+  if (!q.noise && q.heun && !q.traj && !q.coef_table && !q.clamp) {  // plain Heun chain: the lean loop with a second gradient
+    if (q.e.kind == EBM_ENERGY_DOUBLE_WELL)
       hipLaunchKernelGGL((langevin_chain_lean_kernel<EBM_ENERGY_DOUBLE_WELL, false, false, false, true>), grid, block, 0, st, a);
     else
       hipLaunchKernelGGL((langevin_chain_lean_kernel<EBM_ENERGY_HARMONIC, false, false, false, true>), grid, block, 0, st, a);
@@ -302,41 +291,41 @@ int launch_langevin_chain_elem(int kind, float s0, float s1, float* x, int64_t n
   }
   // EBM_CHAIN_CONTRACTED: a permission, used where the contracted kernel exists -- the plain call (constant coefficients, no clamp,
   // no trajectory, the kernels' own draws); every other call computes the reference's arithmetic as before
-  if (contracted && !noise && !heun && !traj && !coef_table && !clamp_on) {
-    if (kind == EBM_ENERGY_DOUBLE_WELL) hipLaunchKernelGGL((langevin_chain_lean_contracted_kernel<EBM_ENERGY_DOUBLE_WELL>), grid, block, 0, st, a);
+  if (q.contracted && !q.noise && !q.heun && !q.traj && !q.coef_table && !q.clamp) {
+    if (q.e.kind == EBM_ENERGY_DOUBLE_WELL) hipLaunchKernelGGL((langevin_chain_lean_contracted_kernel<EBM_ENERGY_DOUBLE_WELL>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((langevin_chain_lean_contracted_kernel<EBM_ENERGY_HARMONIC>), grid, block, 0, st, a);
     return check_launch("ebm_langevin_chain_f32");
   }
-  if (!noise && !heun && (!traj || (dim & 3) == 0)) {
-#define EBM_LEAN_T(KIND, TB, CL)                                                                          \
-  do {                                                                                                   \
-    if (traj) hipLaunchKernelGGL((langevin_chain_lean_kernel<KIND, TB, CL, true>), grid, block, 0, st, a);   \
+  if (!q.noise && !q.heun && (!q.traj || (q.dim & 3) == 0)) {
+#define EBM_LEAN_T(KIND, TB, CL)                                                                             \
+  do {                                                                                                       \
+    if (q.traj) hipLaunchKernelGGL((langevin_chain_lean_kernel<KIND, TB, CL, true>), grid, block, 0, st, a); \
     else hipLaunchKernelGGL((langevin_chain_lean_kernel<KIND, TB, CL, false>), grid, block, 0, st, a);       \
   } while (0)
-#define EBM_LEAN(KIND)                                                 \
-  do {                                                                 \
-    if (coef_table && clamp_on) EBM_LEAN_T(KIND, true, true);          \
-    else if (coef_table) EBM_LEAN_T(KIND, true, false);                \
-    else if (clamp_on) EBM_LEAN_T(KIND, false, true);                  \
-    else EBM_LEAN_T(KIND, false, false);                               \
+#define EBM_LEAN(KIND)                                         \
+  do {                                                         \
+    if (q.coef_table && q.clamp) EBM_LEAN_T(KIND, true, true); \
+    else if (q.coef_table) EBM_LEAN_T(KIND, true, false);      \
+    else if (q.clamp) EBM_LEAN_T(KIND, false, true);           \
+    else EBM_LEAN_T(KIND, false, false);                       \
   } while (0)
-    if (kind == EBM_ENERGY_DOUBLE_WELL) EBM_LEAN(EBM_ENERGY_DOUBLE_WELL);
+    if (q.e.kind == EBM_ENERGY_DOUBLE_WELL) EBM_LEAN(EBM_ENERGY_DOUBLE_WELL);
     else EBM_LEAN(EBM_ENERGY_HARMONIC);
 #undef EBM_LEAN
 #undef EBM_LEAN_T
     return check_launch("ebm_langevin_chain_f32");
   }
-#define EBM_LAUNCH(KIND)                                                                         \
-  do {                                                                                           \
-    if (heun && noise) hipLaunchKernelGGL((langevin_chain_elem_kernel<KIND, true, true>), grid, block, 0, st, a);    \
-    else if (heun) hipLaunchKernelGGL((langevin_chain_elem_kernel<KIND, false, true>), grid, block, 0, st, a);       \
-    else if (noise) hipLaunchKernelGGL((langevin_chain_elem_kernel<KIND, true, false>), grid, block, 0, st, a);      \
-    else hipLaunchKernelGGL((langevin_chain_elem_kernel<KIND, false, false>), grid, block, 0, st, a);                \
+#define EBM_LAUNCH(KIND)                                                                                              \
+  do {                                                                                                                \
+    if (q.heun && q.noise) hipLaunchKernelGGL((langevin_chain_elem_kernel<KIND, true, true>), grid, block, 0, st, a); \
+    else if (q.heun) hipLaunchKernelGGL((langevin_chain_elem_kernel<KIND, false, true>), grid, block, 0, st, a);      \
+    else if (q.noise) hipLaunchKernelGGL((langevin_chain_elem_kernel<KIND, true, false>), grid, block, 0, st, a);     \
+    else hipLaunchKernelGGL((langevin_chain_elem_kernel<KIND, false, false>), grid, block, 0, st, a);                 \
   } while (0)
-  if (kind == EBM_ENERGY_DOUBLE_WELL) EBM_LAUNCH(EBM_ENERGY_DOUBLE_WELL);
+  if (q.e.kind == EBM_ENERGY_DOUBLE_WELL) EBM_LAUNCH(EBM_ENERGY_DOUBLE_WELL);
   else EBM_LAUNCH(EBM_ENERGY_HARMONIC);
 #undef EBM_LAUNCH
-  return check_launch(heun ? "ebm_langevin_heun_chain_f32" : "ebm_langevin_chain_f32");
+  return check_launch(q.heun ? "ebm_langevin_heun_chain_f32" : "ebm_langevin_chain_f32");
 }
 
 }  // namespace ebm

@@ -2,8 +2,7 @@
 // langevin_diag.hip: the variants that also emit diagnostics records): update arithmetic, gradient
 // folds, vector load / store helpers, launch arguments and the lean k-fused kernel template.
 #pragma once
-#include "diag.h"
-#include "ebm_common.h"
+#include "chain_launch.h"
 
 namespace ebm {
 namespace {
@@ -82,6 +81,19 @@ struct ChainArgs {
   uint64_t step0;
   diag::DiagArgs diag;  // per-block diagnostics records at the kept steps (DIAG kernels)
 };
+
+// everything but `noise` and `diag`, which the two launchers set apart
+inline ChainArgs elem_chain_args(const LangevinChainReq& q) {
+  ChainArgs a{};
+  a.x = q.x; a.n_elem = q.n_chains * (int64_t)q.dim; a.dim = q.dim; a.k_steps = q.k_steps;
+  a.c = StepCoef{q.eta, q.sqrt_eta, q.noise_coef};
+  a.table = reinterpret_cast<const float4*>(q.coef_table);
+  a.clamp_on = q.clamp; a.cmin = q.cmin; a.cmax = q.cmax;
+  a.thin = q.thin; a.n_kept = q.n_kept(); a.traj = q.traj;
+  a.s0 = q.e.s[0]; a.s1 = q.e.s[1];
+  a.key = q.key(); a.step0 = q.offset;
+  return a;
+}
 
 extern __shared__ __attribute__((aligned(16))) float elem_smem[];
 

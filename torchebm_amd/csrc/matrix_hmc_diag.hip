@@ -7,9 +7,6 @@
 
 namespace ebm {
 
-bool gauss_hmc_mfma_supported(int32_t dim, int32_t mass_kind);
-bool gauss_hmc_stream_supported(const ebm_energy_t& e, int32_t dim);  // gauss_hmc_stream.hip
-
 bool matrix_hmc_diag_plan(const ebm_energy_t& e, int64_t n_chains, int32_t dim, diag::DiagArgs& d) {
   const bool gauss = e.kind == EBM_ENERGY_GAUSSIAN && (gauss_hmc_mfma_supported(dim, EBM_MASS_NONE) || gauss_hmc_stream_supported(e, dim));
   const bool mix = e.kind == EBM_ENERGY_GMM && dim >= (e.n_comp > 8 ? 12 : 20) && dim <= 96 && dim % 4 == 0 && e.n_comp >= 1 && e.n_comp <= 32 &&
@@ -47,16 +44,13 @@ int launch_diag(const GaussHmcArgs& a, bool mixture, hipStream_t st) {
 }
 }  // namespace
 
-int launch_hmc_chain_matrix_diag(const ebm_energy_t& e, float* x, int64_t n_chains, int32_t dim, int32_t n_mh,
-                                 int32_t n_leapfrog, float eps, const float* eps_table, int32_t mass_kind,
-                                 double mass_scalar, const float* mass_diag, int32_t thin, float* traj, uint8_t* accept_mask,
-                                 uint32_t* accept_count, const float* p_noise, const float* u, uint64_t seed,
-                                 uint64_t offset, float* diag_partials, hipStream_t st) {
-  GaussHmcArgs a = matrix_hmc_args(e, x, n_chains, dim, n_mh, n_leapfrog, eps, eps_table, mass_kind, mass_scalar, mass_diag, thin,
-                                   traj, accept_mask, accept_count, p_noise, u, seed, offset);
-  if (!matrix_hmc_diag_plan(e, n_chains, dim, a.diag))
+int launch_hmc_chain_matrix_diag(const HmcChainReq& q, hipStream_t st) {
+  const ebm_energy_t& e = q.e;
+  const int32_t dim = q.dim;
+  GaussHmcArgs a = matrix_hmc_args(q);
+  if (!matrix_hmc_diag_plan(e, q.n_chains, dim, a.diag))
     return fail(EBM_EDIM, "ebm_hmc_chain_f32: no matrix-layout diagnostics records for this energy / dim %d", dim);
-  a.diag.partials = diag_partials;
+  a.diag.partials = q.diag_partials;
   const bool mixture = e.kind == EBM_ENERGY_GMM;
   return a.mass_diag ? launch_diag<true>(a, mixture, st) : launch_diag<false>(a, mixture, st);
 }

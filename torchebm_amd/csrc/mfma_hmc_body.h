@@ -13,8 +13,7 @@
 // reject), which costs 256 B per chain and transition and no registers.
 #pragma once
 #include <type_traits>
-#include "diag.h"
-#include "ebm_common.h"
+#include "chain_launch.h"
 #include "gauss_bf16x3.h"
 #include "gmm_bf16x3.h"
 
@@ -729,22 +728,12 @@ int launch_policy(const GaussHmcArgs& a, hipStream_t st) {
 
 
 // the common part of the argument block
-inline GaussHmcArgs matrix_hmc_args(const ebm_energy_t& e, float* x, int64_t n_chains, int32_t dim, int32_t n_mh, int32_t n_leapfrog,
-                                    float eps, const float* eps_table, int32_t mass_kind, double mass_scalar,
-                                    const float* mass_diag, int32_t thin, float* traj, uint8_t* accept_mask,
-                                    uint32_t* accept_count, const float* p_noise, const float* u, uint64_t seed, uint64_t offset) {
+inline GaussHmcArgs matrix_hmc_args(const HmcChainReq& q) {
+  const ebm_energy_t& e = q.e;
   GaussHmcArgs a{};
-  a.x = x; a.n_chains = n_chains; a.dim = dim; a.n_mh = n_mh; a.n_leapfrog = n_leapfrog;
-  a.eps = eps; a.eps_table = eps_table;
-  a.has_mass = mass_kind == EBM_MASS_SCALAR;
-  a.mass_raw = (float)mass_scalar;
-  a.mass_sqrt = (float)sqrt(mass_scalar);
-  a.mass_safe = (float)(mass_scalar < 1e-10 ? 1e-10 : mass_scalar);
-  a.thin = thin; a.n_kept = n_mh / thin; a.traj = traj;
-  a.accept_mask = accept_mask; a.accept_count = accept_count; a.p_noise = p_noise; a.u = u;
-  a.key = RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)};
-  a.step0 = offset;
-  a.mass_diag = mass_kind == EBM_MASS_DIAG ? mass_diag : nullptr;
+  fill_hmc(a, q);
+  a.has_mass = q.mass_kind == EBM_MASS_SCALAR;
+  a.mass_diag = q.mass_kind == EBM_MASS_DIAG ? q.mass_diag : nullptr;
   const bool mixture = e.kind == EBM_ENERGY_GMM;
   a.mean = mixture ? nullptr : e.dev0; a.prec = mixture ? nullptr : e.dev1;
   a.prec_image = (!mixture && e.kind == EBM_ENERGY_GAUSSIAN) ? reinterpret_cast<const char*>(e.aux) : nullptr;

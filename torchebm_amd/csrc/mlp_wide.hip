@@ -26,6 +26,7 @@
 // consume them.  The LDS instead parks s1 = silu'(a1) (128 values per lane, idle across both W2 contractions), which
 // keeps the live set at two hidden-width tiles sets + the state: ~330-400 of the 512 registers.
 // Reference: torchebm/samplers/langevin_dynamics.py:154-185 (the loop), core/base_integrator.py:711-731 (the update).
+#include "chain_launch.h"
 #include "mlp_wide_body.h"
 
 namespace ebm {
@@ -42,23 +43,15 @@ bool mlp_wide_supported(int32_t hidden, int32_t dim) {
 }
 
 // k_steps == 0: evaluation into energy_out / grad_out; else the k-fused chain
-int launch_mlp_wide(int32_t hidden, const float* params, float* x, int64_t n_chains, int32_t dim, int32_t k_steps, float eta,
-                    float sqrt_eta, float noise_coef, const float* coef_table, int clamp_on, float cmin, float cmax,
-                    int32_t thin, float* traj, const float* noise, uint64_t seed, uint64_t offset, float* energy_out,
-                    float* grad_out, float* diag_partials, const void* w1_image, hipStream_t st, const char* who,
-                    const uint64_t* rng_dev) {
+int launch_mlp_wide(const LangevinChainReq& q, float* energy_out, float* grad_out, hipStream_t st, const char* who) {
   WideArgs a{};
-  a.rng_dev = rng_dev;
-  a.w1_image = static_cast<const char*>(w1_image);
-  a.x = x; a.n_chains = n_chains; a.dim = dim; a.k_steps = k_steps;
-  a.eta = eta; a.sqrt_eta = sqrt_eta; a.noise_coef = noise_coef;
-  a.table = reinterpret_cast<const float4*>(coef_table);
-  a.clamp_on = clamp_on; a.cmin = cmin; a.cmax = cmax;
-  a.thin = thin; a.n_kept = thin > 0 ? k_steps / thin : 0; a.traj = traj; a.noise = noise;
-  a.key = RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)};
-  a.step0 = offset; a.params = params; a.energy_out = energy_out; a.grad_out = grad_out;
-  a.diag_partials = diag_partials; a.diag_blocks = ceil_div64(n_chains, 32);
-  const int dt = (dim + 31) / 32;
+  fill_langevin(a, q);
+  a.rng_dev = q.rng_dev;
+  a.w1_image = reinterpret_cast<const char*>(q.e.aux);
+  a.params = q.e.dev0; a.energy_out = energy_out; a.grad_out = grad_out;
+  a.diag_partials = q.diag_partials; a.diag_blocks = ceil_div64(q.n_chains, 32);
+  const int32_t hidden = q.e.n_comp;
+  const int dt = (q.dim + 31) / 32;
 #define EBM_WIDE(HTV)                                    \
   switch (dt) {                                          \
     case 1: return launch_one<HTV, 1>(a, st, who);       \

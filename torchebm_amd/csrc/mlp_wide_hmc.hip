@@ -9,6 +9,7 @@
 // xor-32 shuffle each).  RNG coordinates as in hmc_kernel.h: momentum at step 2t, uniforms at 2t + 1 -- the same
 // (seed, step, element) field as every other route.
 // Reference: torchebm/samplers/hmc.py:201-315 (transition, accept), integrators/leapfrog.py:116-187 (safe-mode leapfrog).
+#include "chain_launch.h"
 #include "mlp_wide_hmc_body.h"
 
 namespace ebm {
@@ -27,24 +28,15 @@ bool mlp_wide_hmc_supported(int32_t hidden, int32_t dim) {
 #endif
 }
 
-int launch_hmc_chain_mlp_wide(int32_t hidden, const float* params, float* x, int64_t n_chains, int32_t dim, int32_t n_mh,
-                              int32_t n_leapfrog, float eps, const float* eps_table, int32_t mass_kind, double mass_scalar,
-                              const float* mass_diag, int32_t thin, float* traj, uint8_t* accept_mask, uint32_t* accept_count,
-                              const float* p_noise, const float* u, uint64_t seed, uint64_t offset, float* diag_partials,
-                              const void* w1_image, hipStream_t st, const char* who) {
+int launch_hmc_chain_mlp_wide(const HmcChainReq& q, hipStream_t st, const char* who) {
   widemlp::WideHmcArgs a{};
-  a.w1_image = static_cast<const char*>(w1_image);
-  a.x = x; a.n_chains = n_chains; a.dim = dim; a.n_mh = n_mh; a.n_leapfrog = n_leapfrog;
-  a.eps = eps; a.eps_table = eps_table; a.mass_kind = mass_kind;
-  a.mass_raw = (float)mass_scalar;
-  a.mass_sqrt = (float)sqrt(mass_scalar);
-  a.mass_safe = (float)(mass_scalar < 1e-10 ? 1e-10 : mass_scalar);
-  a.mass_diag = mass_diag; a.thin = thin; a.n_kept = n_mh / thin; a.traj = traj;
-  a.accept_mask = accept_mask; a.accept_count = accept_count; a.p_noise = p_noise; a.u = u;
-  a.key = RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)};
-  a.step0 = offset; a.params = params;
-  a.diag_partials = diag_partials; a.diag_blocks = ceil_div64(n_chains, 32);
-  const int dt = (dim + 31) / 32;
+  fill_hmc(a, q);
+  a.w1_image = reinterpret_cast<const char*>(q.e.aux);
+  a.mass_kind = q.mass_kind; a.mass_diag = q.mass_diag;
+  a.params = q.e.dev0;
+  a.diag_partials = q.diag_partials; a.diag_blocks = ceil_div64(q.n_chains, 32);
+  const int32_t hidden = q.e.n_comp;
+  const int dt = (q.dim + 31) / 32;
 #define EBM_WIDE_HMC(HTV)                                               \
   switch (dt) {                                                         \
     case 1: return widemlp::launch_hmc_one<HTV, 1, false>(a, st, who);        \
@@ -52,7 +44,7 @@ int launch_hmc_chain_mlp_wide(int32_t hidden, const float* params, float* x, int
     case 3: return widemlp::launch_hmc_one<HTV, 3, false>(a, st, who);        \
     default: return widemlp::launch_hmc_one<HTV, 4, false>(a, st, who);       \
   }
-  if (hidden != 256 && mass_kind == EBM_MASS_DIAG) return launch_hmc_mlp_wide_diag(a, hidden, dt, st, who);
+  if (hidden != 256 && q.mass_kind == EBM_MASS_DIAG) return launch_hmc_mlp_wide_diag(a, hidden, dt, st, who);
   if (hidden == 64) { EBM_WIDE_HMC(2) }
   if (hidden == 128) { EBM_WIDE_HMC(4) }
 #undef EBM_WIDE_HMC

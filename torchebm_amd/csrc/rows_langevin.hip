@@ -2,6 +2,7 @@
 // (Gaussian, Gaussian mixture), and the stand-alone energy / gradient kernel.
 // Layout and energies: rows.h.  Reference: torchebm/samplers/langevin_dynamics.py:154-185,
 // torchebm/core/base_integrator.py:711-731, torchebm/core/base_model.py:181-210.
+#include "chain_launch.h"
 #include "rows.h"
 
 namespace ebm {
@@ -401,35 +402,28 @@ bool rows_langevin_diag_plan(const ebm_energy_t& e, int heun, int64_t n_chains, 
   return diag::plan(n_chains, dim, (int64_t)(kBlock / geo.G) * dim, d);
 }
 
-int launch_langevin_chain_rows(const ebm_energy_t& e, float* x, int64_t n_chains, int32_t dim,
-                               int32_t k_steps, float eta, float sqrt_eta, float noise_coef,
-                               const float* coef_table, int clamp_on, float cmin, float cmax,
-                               int32_t thin, float* traj, const float* noise, uint64_t seed,
-                               uint64_t offset, int heun, float* diag_partials, hipStream_t st) {
+int launch_langevin_chain_rows(const LangevinChainReq& q, hipStream_t st) {
+  const ebm_energy_t& e = q.e;
+  const int32_t dim = q.dim;
+  const int heun = q.heun;
   Geometry geo;
   bool lane_per_chain;
   if (!rows_langevin_geometry(e, dim, heun, geo, lane_per_chain))
     return fail(EBM_EDIM, "ebm_langevin_chain_f32: dim %d > 1024 is not supported for this energy", dim);
   RowChainArgs a{};
-  a.x = x; a.n_chains = n_chains; a.dim = dim; a.k_steps = k_steps;
-  a.eta = eta; a.sqrt_eta = sqrt_eta; a.noise_coef = noise_coef;
-  a.table = reinterpret_cast<const float4*>(coef_table);
-  a.clamp_on = clamp_on; a.cmin = cmin; a.cmax = cmax;
-  a.thin = thin; a.n_kept = k_steps / thin; a.traj = traj; a.noise = noise;
-  a.key = RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)};
-  a.step0 = offset;
+  fill_langevin(a, q);
   size_t smem = 0;
   plan_params(e, dim, geo, a.energy, a.param_floats, smem);
   a.diag = diag::DiagArgs{nullptr, 0, 0, 0};
   a.diag_offset_floats = (int)(smem / sizeof(float));
-  if (diag_partials) {
-    if (!rows_langevin_diag_plan(e, heun, n_chains, dim, a.diag))
+  if (q.diag_partials) {
+    if (!rows_langevin_diag_plan(e, heun, q.n_chains, dim, a.diag))
       return fail(EBM_EDIM, "ebm_langevin_chain_f32: diagnostics records are not available for this energy / dim %d", dim);
-    a.diag.partials = diag_partials;
+    a.diag.partials = q.diag_partials;
     smem += (size_t)diag::lds_floats(a.diag.E, a.diag.S) * sizeof(float);
   }
   const bool pair = rows_langevin_pair(e, dim);
-  const int64_t blocks = pair ? ceil_div64(n_chains, 2 * (int64_t)kBlock) : blocks_for(n_chains, geo);
+  const int64_t blocks = pair ? ceil_div64(q.n_chains, 2 * (int64_t)kBlock) : blocks_for(q.n_chains, geo);
   if (blocks > 0x7fffffffLL) return fail(EBM_EINVAL, "ebm_langevin_chain_f32: too many chains for one launch");
   const dim3 grid((unsigned)blocks), block(kBlock);
   if (pair && e.kind == EBM_ENERGY_GAUSSIAN) {
