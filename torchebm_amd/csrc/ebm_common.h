@@ -64,7 +64,7 @@ struct U4 {
   uint32_t x, y, z, w;
 };
 
-__device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
+__host__ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
 #if defined(__HIP_DEVICE_COMPILE__)
   return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
 #else
@@ -72,7 +72,7 @@ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
 #endif
 }
 
-__device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
+__host__ __device__ __forceinline__ U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                             uint32_t k0, uint32_t k1) {
 #pragma unroll
   for (int r = 0; r < 10; ++r) {
@@ -96,10 +96,64 @@ struct RngKey {
   uint32_t k0, k1;  // seed
 };
 
-__device__ __forceinline__ U4 philox_at(RngKey key, uint64_t group, uint64_t step) {
+__host__ __device__ __forceinline__ U4 philox_at(RngKey key, uint64_t group, uint64_t step) {
   return philox4x32_10((uint32_t)group, (uint32_t)(group >> 32), (uint32_t)step,
                        (uint32_t)(step >> 32), key.k0, key.k1);
 }
+
+// Philox4x32-10 of one lane whose counter high words are zero: counter (group, 0, step, 0), group fixed for the lane and
+// step the same for the whole wave -- the k-fused element-wise chains whenever the group count and the launch's last step fit
+// 32 bits.  The first two rounds then split into a lane-invariant part (built once: M0*group, then M1*(hi(M0*group) ^ k1)) and a
+// wave-uniform part (per step, on the scalar unit: M1*step, then M0*(hi(M1*step) ^ k0)), joined by two 2-input XORs; only
+// rounds 3-10 are vector multiplies.  16 v_mad_u64_u32 + 16 v_bitop3 + 2 v_xor per draw where philox_at issues 18 + 20.
+// at(step) == philox4x32_10(group, 0, step, 0, k0, k1) bit for bit (tests/test_philox_lane32.py); philox_at stays the
+// 64-bit definition for every other counter.
+struct PhiloxLane32 {
+  uint32_t c3_1;      // round 1's c3: lo(M0*group)
+  uint32_t hi2, lo2;  // round 2's lane-invariant product M1*(hi(M0*group) ^ k1)
+  uint32_t k0, k1;    // the key (wave-uniform)
+
+  __host__ __device__ __forceinline__ PhiloxLane32(uint32_t group, RngKey key) : k0(key.k0), k1(key.k1) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * group;
+    c3_1 = (uint32_t)p0;
+    const uint64_t p1 = (uint64_t)0xCD9E8D57u * ((uint32_t)(p0 >> 32) ^ key.k1);
+    hi2 = (uint32_t)(p1 >> 32);
+    lo2 = (uint32_t)p1;
+  }
+
+  // `step` must be wave-uniform (a kernel argument plus the loop counter): the compiler then keeps the four step multiplies
+  // and the uniform XORs on the scalar unit by itself.  No readfirstlane here -- it is convergent, and a convergent call in
+  // the step loop stops LLVM from unrolling it by two (tests/test_isa_lean_philox.py checks both).
+  __host__ __device__ __forceinline__ U4 at(uint32_t step) const {
+    // round 1, wave-uniform half: c1 = lo(M1*step), c0' = hi(M1*step) ^ k0
+    const uint64_t q1 = (uint64_t)0xCD9E8D57u * step;
+    const uint32_t c1_1 = (uint32_t)q1;
+    const uint32_t c0_1 = (uint32_t)(q1 >> 32) ^ k0;
+    // round 2 (key + 1 bump): the uniform product M0*c0' against the lane's M1*c2'
+    const uint32_t rk0 = k0 + 0x9E3779B9u, rk1 = k1 + 0xBB67AE85u;
+    const uint64_t q2 = (uint64_t)0xD2511F53u * c0_1;
+    uint32_t c0 = hi2 ^ (c1_1 ^ rk0);
+    uint32_t c2 = ((uint32_t)(q2 >> 32) ^ rk1) ^ c3_1;
+    uint32_t c1 = lo2;
+    uint32_t c3 = (uint32_t)q2;
+    uint32_t r0 = rk0 + 0x9E3779B9u, r1 = rk1 + 0xBB67AE85u;
+    // rounds 3-10: philox4x32_10's round, unchanged
+#pragma unroll
+    for (int r = 2; r < 10; ++r) {
+      const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
+      const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
+      const uint32_t n0 = xor3((uint32_t)(p1 >> 32), c1, r0);
+      const uint32_t n2 = xor3((uint32_t)(p0 >> 32), c3, r1);
+      c1 = (uint32_t)p1;
+      c3 = (uint32_t)p0;
+      c0 = n0;
+      c2 = n2;
+      r0 += 0x9E3779B9u;
+      r1 += 0xBB67AE85u;
+    }
+    return U4{c0, c1, c2, c3};
+  }
+};
 
 // (0, 1]: never 0, so the log below is finite; same mapping as cuRAND's uniform.
 __device__ __forceinline__ float u01_open_low(uint32_t r) {
@@ -123,19 +177,19 @@ struct F4 {
   float v[4];
 };
 
-__device__ __forceinline__ F4 normal4_at(RngKey key, uint64_t group, uint64_t step) {
-  const U4 o = philox_at(key, group, step);
+__device__ __forceinline__ F4 normal4_of(U4 o) {
   F4 n;
   box_muller(o.x, o.y, n.v[0], n.v[1]);
   box_muller(o.z, o.w, n.v[2], n.v[3]);
   return n;
 }
 
+__device__ __forceinline__ F4 normal4_at(RngKey key, uint64_t group, uint64_t step) { return normal4_of(philox_at(key, group, step)); }
+
 // The contracted form (ABI 8, EBM_CHAIN_CONTRACTED): the Box-Muller radius carries the update's whole noise coefficient
 // A = noise_coef * sqrt_eta, so the update adds the draw as it is -- one multiply per PAIR of normals where the reference order
 // (eps * sqrt_eta, then * noise_coef) spends two per normal.  Same Philox counters; rounding differs in the last bit.
-__device__ __forceinline__ F4 scaled_normal4_at(RngKey key, uint64_t group, uint64_t step, float A) {
-  const U4 o = philox_at(key, group, step);
+__device__ __forceinline__ F4 scaled_normal4_of(U4 o, float A) {
   F4 n;
   const float r0 = A * __builtin_amdgcn_sqrtf(-1.38629436111989061883f * __builtin_amdgcn_logf(u01_open_low(o.x)));
   const float r1 = A * __builtin_amdgcn_sqrtf(-1.38629436111989061883f * __builtin_amdgcn_logf(u01_open_low(o.z)));
@@ -145,6 +199,10 @@ __device__ __forceinline__ F4 scaled_normal4_at(RngKey key, uint64_t group, uint
   n.v[2] = r1 * __builtin_amdgcn_sinf(v1);
   n.v[3] = r1 * __builtin_amdgcn_cosf(v1);
   return n;
+}
+
+__device__ __forceinline__ F4 scaled_normal4_at(RngKey key, uint64_t group, uint64_t step, float A) {
+  return scaled_normal4_of(philox_at(key, group, step), A);
 }
 
 __device__ __forceinline__ uint32_t pick(U4 o, int r) {

@@ -274,33 +274,27 @@ int launch_langevin_step(const float* x, const float* grad, float* out, const fl
   return check_launch("ebm_langevin_step_f32");
 }
 
-int launch_langevin_chain_elem(const LangevinChainReq& q, hipStream_t st) {
-  ChainArgs a = elem_chain_args(q);
-  a.noise = q.noise;
-  a.diag = diag::DiagArgs{nullptr, 0, 0, 0};
-  const int64_t n_groups = ceil_div64(a.n_elem, 4);
-  const int64_t blocks = ceil_div64(n_groups, kBlock);
-  if (blocks > 0x7fffffffLL) return fail(EBM_EINVAL, "state too large for one launch (%lld blocks)", (long long)blocks);
-  const dim3 grid((unsigned)blocks), block(kBlock);
-  if (!q.noise && q.heun && !q.traj && !q.coef_table && !q.clamp) {  // plain Heun chain: the lean loop with a second gradient
+// The lean k-fused kernels (no external noise) at one Philox counter width (langevin_elem.h lean_counters32).
+template <bool C64>
+int launch_langevin_chain_lean(const LangevinChainReq& q, const ChainArgs& a, dim3 grid, dim3 block, hipStream_t st) {
+  if (q.heun) {  // plain Heun chain: the lean loop with a second gradient
     if (q.e.kind == EBM_ENERGY_DOUBLE_WELL)
-      hipLaunchKernelGGL((langevin_chain_lean_kernel<EBM_ENERGY_DOUBLE_WELL, false, false, false, true>), grid, block, 0, st, a);
+      hipLaunchKernelGGL((langevin_chain_lean_kernel<EBM_ENERGY_DOUBLE_WELL, false, false, false, true, C64>), grid, block, 0, st, a);
     else
-      hipLaunchKernelGGL((langevin_chain_lean_kernel<EBM_ENERGY_HARMONIC, false, false, false, true>), grid, block, 0, st, a);
+      hipLaunchKernelGGL((langevin_chain_lean_kernel<EBM_ENERGY_HARMONIC, false, false, false, true, C64>), grid, block, 0, st, a);
     return check_launch("ebm_langevin_heun_chain_f32");
   }
   // EBM_CHAIN_CONTRACTED: a permission, used where the contracted kernel exists -- the plain call (constant coefficients, no clamp,
   // no trajectory, the kernels' own draws); every other call computes the reference's arithmetic as before
-  if (q.contracted && !q.noise && !q.heun && !q.traj && !q.coef_table && !q.clamp) {
-    if (q.e.kind == EBM_ENERGY_DOUBLE_WELL) hipLaunchKernelGGL((langevin_chain_lean_contracted_kernel<EBM_ENERGY_DOUBLE_WELL>), grid, block, 0, st, a);
-    else hipLaunchKernelGGL((langevin_chain_lean_contracted_kernel<EBM_ENERGY_HARMONIC>), grid, block, 0, st, a);
+  if (q.contracted && !q.traj && !q.coef_table && !q.clamp) {
+    if (q.e.kind == EBM_ENERGY_DOUBLE_WELL) hipLaunchKernelGGL((langevin_chain_lean_contracted_kernel<EBM_ENERGY_DOUBLE_WELL, C64>), grid, block, 0, st, a);
+    else hipLaunchKernelGGL((langevin_chain_lean_contracted_kernel<EBM_ENERGY_HARMONIC, C64>), grid, block, 0, st, a);
     return check_launch("ebm_langevin_chain_f32");
   }
-  if (!q.noise && !q.heun && (!q.traj || (q.dim & 3) == 0)) {
-#define EBM_LEAN_T(KIND, TB, CL)                                                                             \
-  do {                                                                                                       \
-    if (q.traj) hipLaunchKernelGGL((langevin_chain_lean_kernel<KIND, TB, CL, true>), grid, block, 0, st, a); \
-    else hipLaunchKernelGGL((langevin_chain_lean_kernel<KIND, TB, CL, false>), grid, block, 0, st, a);       \
+#define EBM_LEAN_T(KIND, TB, CL)                                                                                  \
+  do {                                                                                                            \
+    if (q.traj) hipLaunchKernelGGL((langevin_chain_lean_kernel<KIND, TB, CL, true, false, C64>), grid, block, 0, st, a); \
+    else hipLaunchKernelGGL((langevin_chain_lean_kernel<KIND, TB, CL, false, false, C64>), grid, block, 0, st, a);       \
   } while (0)
 #define EBM_LEAN(KIND)                                         \
   do {                                                         \
@@ -309,12 +303,24 @@ int launch_langevin_chain_elem(const LangevinChainReq& q, hipStream_t st) {
     else if (q.clamp) EBM_LEAN_T(KIND, false, true);           \
     else EBM_LEAN_T(KIND, false, false);                       \
   } while (0)
-    if (q.e.kind == EBM_ENERGY_DOUBLE_WELL) EBM_LEAN(EBM_ENERGY_DOUBLE_WELL);
-    else EBM_LEAN(EBM_ENERGY_HARMONIC);
+  if (q.e.kind == EBM_ENERGY_DOUBLE_WELL) EBM_LEAN(EBM_ENERGY_DOUBLE_WELL);
+  else EBM_LEAN(EBM_ENERGY_HARMONIC);
 #undef EBM_LEAN
 #undef EBM_LEAN_T
-    return check_launch("ebm_langevin_chain_f32");
-  }
+  return check_launch("ebm_langevin_chain_f32");
+}
+
+int launch_langevin_chain_elem(const LangevinChainReq& q, hipStream_t st) {
+  ChainArgs a = elem_chain_args(q);
+  a.noise = q.noise;
+  a.diag = diag::DiagArgs{nullptr, 0, 0, 0};
+  const int64_t n_groups = ceil_div64(a.n_elem, 4);
+  const int64_t blocks = ceil_div64(n_groups, kBlock);
+  if (blocks > 0x7fffffffLL) return fail(EBM_EINVAL, "state too large for one launch (%lld blocks)", (long long)blocks);
+  const dim3 grid((unsigned)blocks), block(kBlock);
+  // the lean loop: Heun without table, clamp or trajectory; Euler-Maruyama with float4 trajectory rows or none
+  const bool lean = !q.noise && (q.heun ? (!q.traj && !q.coef_table && !q.clamp) : (!q.traj || (q.dim & 3) == 0));
+  if (lean) return lean_counters32(a) ? launch_langevin_chain_lean<false>(q, a, grid, block, st) : launch_langevin_chain_lean<true>(q, a, grid, block, st);
 #define EBM_LAUNCH(KIND)                                                                                              \
   do {                                                                                                                \
     if (q.heun && q.noise) hipLaunchKernelGGL((langevin_chain_elem_kernel<KIND, true, true>), grid, block, 0, st, a); \

@@ -14,20 +14,12 @@ bool elem_diag_supported(int32_t dim, bool has_noise, bool has_traj) {
 
 bool elem_diag_plan(int64_t n_chains, int32_t dim, diag::DiagArgs& d) { return diag::plan(n_chains, dim, kBlock * 4, d); }
 
-int launch_langevin_chain_elem_diag(const LangevinChainReq& q, hipStream_t st) {
-  const char* who = q.heun ? "ebm_langevin_heun_chain_f32" : "ebm_langevin_chain_f32";
-  const int32_t dim = q.dim;
-  ChainArgs a = elem_chain_args(q);
-  if (!elem_diag_plan(q.n_chains, dim, a.diag)) return fail(EBM_EDIM, "%s: diagnostics records need dim | 1024 or 1024 | dim on the flat kernel (dim %d)", who, dim);
-  a.diag.partials = q.diag_partials;
-  if (a.diag.n_blocks > 0x7fffffffLL) return fail(EBM_EINVAL, "%s: state too large for one launch", who);
-  const dim3 grid((unsigned)a.diag.n_blocks), block(kBlock);
-  const int lds_generic = diag::lds_floats(a.diag.E, a.diag.S), lds_fast = 2 * diag::fast_lds_floats();
-  const size_t smem = (size_t)(diag::fast_flat_ok(dim) ? lds_fast : lds_generic) * sizeof(float);
-#define EBM_D_T(KIND, TB, CL, HE)                                                                                        \
-  do {                                                                                                                   \
-    if (q.traj) hipLaunchKernelGGL((langevin_chain_lean_diag_kernel<KIND, TB, CL, true, HE>), grid, block, smem, st, a); \
-    else hipLaunchKernelGGL((langevin_chain_lean_diag_kernel<KIND, TB, CL, false, HE>), grid, block, smem, st, a);       \
+template <bool C64>
+static int launch_diag(const LangevinChainReq& q, const ChainArgs& a, dim3 grid, dim3 block, size_t smem, hipStream_t st) {
+#define EBM_D_T(KIND, TB, CL, HE)                                                                                             \
+  do {                                                                                                                        \
+    if (q.traj) hipLaunchKernelGGL((langevin_chain_lean_diag_kernel<KIND, TB, CL, true, HE, C64>), grid, block, smem, st, a); \
+    else hipLaunchKernelGGL((langevin_chain_lean_diag_kernel<KIND, TB, CL, false, HE, C64>), grid, block, smem, st, a);       \
   } while (0)
 #define EBM_D_H(KIND, HE)                                       \
   do {                                                          \
@@ -46,7 +38,20 @@ int launch_langevin_chain_elem_diag(const LangevinChainReq& q, hipStream_t st) {
 #undef EBM_D
 #undef EBM_D_H
 #undef EBM_D_T
-  return check_launch(who);
+  return check_launch(q.heun ? "ebm_langevin_heun_chain_f32" : "ebm_langevin_chain_f32");
+}
+
+int launch_langevin_chain_elem_diag(const LangevinChainReq& q, hipStream_t st) {
+  const char* who = q.heun ? "ebm_langevin_heun_chain_f32" : "ebm_langevin_chain_f32";
+  const int32_t dim = q.dim;
+  ChainArgs a = elem_chain_args(q);
+  if (!elem_diag_plan(q.n_chains, dim, a.diag)) return fail(EBM_EDIM, "%s: diagnostics records need dim | 1024 or 1024 | dim on the flat kernel (dim %d)", who, dim);
+  a.diag.partials = q.diag_partials;
+  if (a.diag.n_blocks > 0x7fffffffLL) return fail(EBM_EINVAL, "%s: state too large for one launch", who);
+  const dim3 grid((unsigned)a.diag.n_blocks), block(kBlock);
+  const int lds_generic = diag::lds_floats(a.diag.E, a.diag.S), lds_fast = 2 * diag::fast_lds_floats();
+  const size_t smem = (size_t)(diag::fast_flat_ok(dim) ? lds_fast : lds_generic) * sizeof(float);
+  return lean_counters32(a) ? launch_diag<false>(q, a, grid, block, smem, st) : launch_diag<true>(q, a, grid, block, smem, st);
 }
 
 }  // namespace ebm

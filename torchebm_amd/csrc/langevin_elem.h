@@ -112,9 +112,13 @@ extern __shared__ __attribute__((aligned(16))) float elem_smem[];
 // as n_kept runs of `thin` steps (the hot inner loop is the plain one, unrolled by two).
 // CONTRACT (ABI 8, EBM_CHAIN_CONTRACTED; the opt-in of `sampler.fused_arithmetic = True` on LangevinDynamics): the same step with the arithmetic
 // contracted -- the gradient's x^2 - b^2 and the drift x - eta g as fused multiply-adds, the noise coefficient folded into the
-// Box-Muller radius (ebm_common.h scaled_normal4_at): 8 of the loop's 76 vector instructions per float4 group fewer.  NOT the
+// Box-Muller radius (ebm_common.h scaled_normal4_of): 6 of the loop's 72 vector instructions per float4 group and step fewer
+// (66 against 72; both at 32-bit Philox counters).  NOT the
 // reference's rounding (eager torch rounds every multiply and add); the same law, moments and Philox field.
-template <int KIND, bool TABLE, bool CLAMP, bool TRAJ, bool HEUN, bool DIAG, bool CONTRACT = false>
+// C64: the Philox counter at its full width, (group lo, group hi, step lo, step hi).  Otherwise (lean_counters32) both high
+// words are 0 for the whole launch and the draw is ebm_common.h's PhiloxLane32: the same numbers, two vector multiplies and
+// four logic ops fewer per float4 group and step (76 -> 72 vector instructions on the plain DoubleWell loop).
+template <int KIND, bool TABLE, bool CLAMP, bool TRAJ, bool HEUN, bool DIAG, bool CONTRACT, bool C64>
 __device__ __forceinline__ void lean_body(const ChainArgs& a) {
   const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const int64_t e0 = g * 4;
@@ -125,6 +129,13 @@ __device__ __forceinline__ void lean_body(const ChainArgs& a) {
   const int nv = left >= 4 ? 4 : (left > 0 ? (int)left : 0);
   F4 x = load4(a.x, e0 < a.n_elem ? e0 : 0, nv, true);
   StepCoef c = a.c;
+  // lanes past the end of the state (DIAG only) draw from a truncated counter and store nothing
+  const PhiloxLane32 rng((uint32_t)g, a.key);
+  const uint32_t step0 = (uint32_t)a.step0;
+  auto draw = [&](int i) -> U4 {
+    if constexpr (C64) return philox_at(a.key, (uint64_t)g, a.step0 + (uint64_t)i);
+    else return rng.at(step0 + (uint32_t)i);
+  };
   // TRAJ (dim % 4 == 0 only, so a lane's float4 never straddles two chains): traj[c, j, d..d+3]
   float* tptr = nullptr;
   if constexpr (TRAJ) {
@@ -138,7 +149,7 @@ __device__ __forceinline__ void lean_body(const ChainArgs& a) {
     }
     if constexpr (CONTRACT) {
       static_assert(!TABLE && !CLAMP && !HEUN, "the contracted form exists for the plain call only");
-      const F4 e = scaled_normal4_at(a.key, (uint64_t)g, a.step0 + (uint64_t)i, c.noise_coef * c.sqrt_eta);  // (uniform product: scalar unit)
+      const F4 e = scaled_normal4_of(draw(i), c.noise_coef * c.sqrt_eta);  // (uniform product: scalar unit)
 #pragma unroll
       for (int q = 0; q < 4; q += 2) {
         const v2f xv = {x.v[q], x.v[q + 1]}, ev = {e.v[q], e.v[q + 1]};
@@ -151,7 +162,7 @@ __device__ __forceinline__ void lean_body(const ChainArgs& a) {
       }
       return;
     }
-    const F4 eps = normal4_at(a.key, (uint64_t)g, a.step0 + (uint64_t)i);
+    const F4 eps = normal4_of(draw(i));
     // gradient + update on explicit 2-vectors (packed-f32 instructions); written out this way because
     // the clamp's min/max would otherwise make the compiler fall back to scalar arithmetic for all of it
 #pragma unroll
@@ -225,21 +236,30 @@ __device__ __forceinline__ void lean_body(const ChainArgs& a) {
   if (nv > 0) store4(a.x, e0, nv, true, x);
 }
 
-template <int KIND, bool TABLE, bool CLAMP, bool TRAJ, bool HEUN = false>
+template <int KIND, bool TABLE, bool CLAMP, bool TRAJ, bool HEUN, bool C64>
 __global__ __launch_bounds__(kBlock) void langevin_chain_lean_kernel(ChainArgs a) {
-  lean_body<KIND, TABLE, CLAMP, TRAJ, HEUN, false>(a);
+  lean_body<KIND, TABLE, CLAMP, TRAJ, HEUN, false, false, C64>(a);
 }
-template <int KIND>
+template <int KIND, bool C64>
 __global__ __launch_bounds__(kBlock) void langevin_chain_lean_contracted_kernel(ChainArgs a) {
-  lean_body<KIND, false, false, false, false, false, true>(a);
+  lean_body<KIND, false, false, false, false, false, true, C64>(a);
 }
 
 // The DIAG form, held to 64 VGPRs (8 waves per SIMD like the plain kernel: the out-of-line generic emit() would
 // otherwise set the kernel's register count to 80 and cost the step loop 4 %).  A template-dependent expression in
 // __launch_bounds__ is ignored by hipcc 7.2, hence the second entry point.
-template <int KIND, bool TABLE, bool CLAMP, bool TRAJ, bool HEUN>
+template <int KIND, bool TABLE, bool CLAMP, bool TRAJ, bool HEUN, bool C64>
 __global__ __launch_bounds__(kBlock, 8) void langevin_chain_lean_diag_kernel(ChainArgs a) {
-  lean_body<KIND, TABLE, CLAMP, TRAJ, HEUN, true>(a);
+  lean_body<KIND, TABLE, CLAMP, TRAJ, HEUN, true, false, C64>(a);
+}
+
+// The lean kernels take the 32-bit counter words (C64 = false) when every lane's group index and every step of the launch fit
+// 32 bits: ceil(n_elem / 4) <= 2^32 and step0 + k_steps <= 2^32 (no carry into the step's high word).  Larger states and
+// generator offsets run the C64 instantiations, whose draws are the same function of the full counter.
+inline bool lean_counters32(const ChainArgs& a) {
+  const uint64_t two32 = 1ull << 32;
+  const uint64_t k = a.k_steps > 0 ? (uint64_t)a.k_steps : 0;
+  return (uint64_t)ceil_div64(a.n_elem, 4) <= two32 && a.step0 <= two32 - k;
 }
 
 }  // namespace
