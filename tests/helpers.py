@@ -118,3 +118,29 @@ def sha16(t):
     import hashlib
 
     return hashlib.sha256(t.contiguous().numpy().tobytes()).hexdigest()[:16]
+
+
+class launched_kernels:
+    """``with launched_kernels() as k: ...`` -- afterwards ``k.names`` are the demangled names of the GPU kernels the block
+    launched, in launch order (torch.profiler, CUDA activity: kineto sees the launches of libebm_hip.so too).  Recording no
+    kernel at all is a failure, not a skip: a profiler that cannot see the library's launches must not pass a route check."""
+
+    def __enter__(self):
+        from torch.profiler import ProfilerActivity, profile
+
+        torch.cuda.synchronize()
+        self._prof = profile(activities=[ProfilerActivity.CUDA])
+        self._prof.__enter__()
+        self.names = []
+        return self
+
+    def __exit__(self, *exc):
+        torch.cuda.synchronize()
+        self._prof.__exit__(*exc)
+        if exc[0] is not None:
+            return False
+        events = [e for e in self._prof.events() if e.device_type == torch.autograd.DeviceType.CUDA]
+        events.sort(key=lambda e: e.time_range.start)
+        self.names = [e.name for e in events if not e.name.startswith(("Memcpy", "Memset"))]
+        assert self.names, "the profiler recorded no GPU kernel: it cannot check a route"
+        return False
