@@ -6,8 +6,12 @@ config 2: DoubleWell(h=2, b=1), n_chains = 2^20, dim = 64, k = 200 Euler-Maruyam
 eta = 0.01, sigma = 1, fp32, initial state N(0, 1) clamped to [-4, 4] and already resident in HBM.  One call = one launch
 of the fused kernel ``ebm_langevin_chain_f32`` = n_chains * k chain-steps.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the dump (if asked for) and
+the JSON line.  ``--full`` adds everything that takes runs of its own, after the timed steps: the roofline probes and the
+counter passes, the CPU baselines, the other BASELINE configs (``extra``) and, at N > 1, the read-back breakdown.
 
 ``--gpus N`` with N > 1 and no torchrun environment (``WORLD_SIZE`` unset) launches the N ranks
 ITSELF: the process re-executes this file under ``torch.distributed.run`` (127.0.0.1 rendezvous, a
@@ -24,8 +28,9 @@ pipelined with the last step (four row blocks; block i's gather is in flight whi
 sampled -- utils.sample_and_gather).  It also runs once after the warm-up steps, untimed, so that
 communicator set-up is not timed.
 
-Output: one JSON line on rank 0 (see DESIGN.md §Measurement for the roofline accounting).  At N = 1
-the line also carries ``extra``: the other BASELINE configs and the genuinely HBM-bound per-step
+Output: one JSON line on rank 0 (see DESIGN.md §Measurement for the roofline accounting).  A plain run's ``roofline``
+holds only what the timed launches' own events give (kernel time, the step-equivalent and physical HBM figures).  With
+``--full`` at N = 1 the line also carries ``extra``: the other BASELINE configs and the genuinely HBM-bound per-step
 kernel, measured in the same run (``--no-extra`` skips them).
 """
 
@@ -77,10 +82,13 @@ def parse():
                     help="4 = BASELINE configs[3]'s per-GPU shard as the timed step (2^20 chains, dim 128, k 500: at 8 ranks "
                          "the timed run IS configs[3]); default 2 = configs[1]")
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"], help="cpu = plumbing dry-run (gloo)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the other BASELINE configs (the `extra` array)")
-    ap.add_argument("--no-traffic", action="store_true", help="do not re-run two launches under rocprofv3 --pmc for roofline.traffic "
-                                                              "(the committed profiles/traffic.json is used instead)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what takes runs of its own: roofline probes and counter passes, "
+                         "CPU baselines, the other BASELINE configs (`extra`), the N > 1 read-back breakdown")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the other BASELINE configs (the `extra` array)")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: do not re-run two launches under rocprofv3 --pmc for "
+                                                              "roofline.traffic (the committed profiles/traffic.json is used instead)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (see dump_outputs)")
     ap.add_argument("--traffic-child", action="store_true", help=argparse.SUPPRESS)  # the process rocprofv3 wraps: three launches, no output
@@ -997,11 +1005,11 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    # ---- N > 1, behind the timed region: WHY the N-rank number is what it is.  The same step three ways, each fenced
-    #      (barrier + device sync) on both sides, median of 3, maximum over ranks: plain (no collective), with the
+    # ---- N > 1 with --full, behind the timed region: WHY the N-rank number is what it is.  The same step three ways, each
+    #      fenced (barrier + device sync) on both sides, median of 3, maximum over ranks: plain (no collective), with the
     #      pipelined read-back (what the timed run's last step does), and the all-gather alone (not overlapped).
     multi = None
-    if world > 1:
+    if world > 1 and args.full:
         import torch.distributed as dist
 
         from torchebm_amd.utils import all_gather_cat
@@ -1069,13 +1077,37 @@ def main():
         valu_rate = None
         if kernel_ms:
             achieved = algo_bytes / (kernel_ms * 1e-3) / 1e9
+            physical = 2 * n * dim * 4  # what the k-fused launch has to move: the state in, the state out
+            # every run: the figures that the timed launches' own events give
+            roof = {
+                # The kernel keeps the state in registers for all k steps, so it is NOT memory-shaped: the physical
+                # limiter is VALU issue (Philox-10 + Box-Muller).  `achieved`/`peak`/`frac` keep BASELINE.json's
+                # definition -- step-equivalent bytes (8*dim per chain-step) over the kernel time against HBM peak --
+                # which for a k-fused kernel exceeds 1; the physical figures are in `hbm_physical` and (--full) `valu`.
+                "bound": "valu",
+                "achieved": achieved,
+                "peak": HBM_PEAK_GBS,
+                "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS,
+                "definition": "step-equivalent: n_chains*k*8*dim bytes / kernel time (BASELINE.md section 3)",
+                "hbm_physical_frac": physical / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                "hbm_physical": {
+                    "bytes_per_launch": physical,
+                    "GBps": physical / (kernel_ms * 1e-3) / 1e9,
+                    "frac_of_peak": physical / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                },
+                "kernel": "langevin_chain_lean_kernel<DoubleWell> (ebm_langevin_chain_f32)",
+                "kernel_ms": kernel_ms,
+                "kernel_ms_per_step": kernel_dist,
+                "algorithmic_bytes_per_launch": algo_bytes,
+            }
+        if kernel_ms and args.full:
             traffic = None if (args.no_traffic or world > 1) else measure_traffic(args)
             if traffic is None:
                 traffic = read_traffic()
             valu_rate = plain_valu_rate(device)
             costs = issue_costs(device)  # per-class issue costs measured in THIS run -> the loop's price
             loop_units = costs["issue_units_per_float4_group_step"]
-            physical = 2 * n * dim * 4  # what the k-fused launch has to move: the state in, the state out
             issue_limit_ms = (n * dim / 4 / 64) * k * loop_units / valu_rate * 1e3
             # the bound: the same number of wave-trips of the loop's exact static instruction mix, issued dependency-free
             mixed_ceiling_ms = (n * dim / 4 / 64) * k * costs["mixed_stream_s_per_wave_trip"] * 1e3
@@ -1100,23 +1132,12 @@ def main():
                            "kernel's measured cycles per trip sit between the two, within a few percent of the rate-class figure (the nominal "
                            "2.4 GHz over-counts cycles when the chip clocks lower): the instruction count, not waiting, is the time",
             }
-            roof = {
-                # The kernel keeps the state in registers for all k steps, so it is NOT memory-shaped: the physical
-                # limiter is VALU issue (Philox-10 + Box-Muller).  `achieved`/`peak`/`frac` keep BASELINE.json's
-                # definition -- step-equivalent bytes (8*dim per chain-step) over the kernel time against HBM peak --
-                # which for a k-fused kernel exceeds 1; the physical figures are in `hbm_physical` and `valu`.
-                "bound": "valu",
-                "achieved": achieved,
-                "peak": HBM_PEAK_GBS,
-                "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS,
-                "definition": "step-equivalent: n_chains*k*8*dim bytes / kernel time (BASELINE.md section 3)",
+            roof.update({
                 # flat copies of the figures that ARE bounds (a consumer that keeps only the top level of this object still gets them):
                 "bound_frac": min(1.0, mixed_ceiling_ms / kernel_ms),          # the one fraction that is <= 1: measured VALU issue ceiling / kernel
                 "valu_frac": mixed_ceiling_ms / kernel_ms,
                 "valu_insts_per_group_step": sum(LEAN_LOOP_MIX.values()),
                 "valu_rate_class_ceiling_frac": independent["kernel_over_rate_class_ceiling"],
-                "hbm_physical_frac": physical / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
                 "valu": {
                     "issue_units_per_float4_group_step": loop_units,
                     "issue_costs_measured_in_run": costs,
@@ -1131,19 +1152,10 @@ def main():
                                           "(classes overlap), NOT a ceiling -- kept for continuity with rounds 1-3",
                     "independent_of_the_probe": independent,
                 },
-                "hbm_physical": {
-                    "bytes_per_launch": physical,
-                    "GBps": physical / (kernel_ms * 1e-3) / 1e9,
-                    "frac_of_peak": physical / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                },
                 "measured_copy_ceiling": copy_ceiling_gbs(device),
                 "traffic": None if not traffic else traffic.get("hbm_bytes_per_launch"),
                 "traffic_source": None if not traffic else traffic.get("source"),
-                "kernel": "langevin_chain_lean_kernel<DoubleWell> (ebm_langevin_chain_f32)",
-                "kernel_ms": kernel_ms,
-                "kernel_ms_per_step": kernel_dist,
-                "algorithmic_bytes_per_launch": algo_bytes,
-            }
+            })
         line = {
             "metric": "MCMC chain-steps/sec",
             "value": value,
@@ -1174,12 +1186,13 @@ def main():
                              else ("torch.distributed.run" if world > 1 else "single process")),
                 "readback": readback,
                 "device": args.device,
+                "full": args.full,  # False: the headline alone (the --full-only fields are null or absent)
             },
             "readback": multi,
             "roofline": roof,
-            "cpu_baseline": None if (args.no_cpu_baseline or world > 1) else cpu_baseline(dim, k),
+            "cpu_baseline": None if (not args.full or args.no_cpu_baseline or world > 1) else cpu_baseline(dim, k),
         }
-        if on_gpu and world == 1 and not args.no_extra:
+        if args.full and on_gpu and world == 1 and not args.no_extra:
             line["extra"] = extra_measurements(device, valu_rate or plain_valu_rate(device),
                                                (roof or {}).get("valu", {}).get("issue_units_per_float4_group_step") or LEAN_LOOP_ISSUE_UNITS,
                                                cpu=not args.no_cpu_baseline,

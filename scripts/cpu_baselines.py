@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """CPU baselines for configs 3 and 5: the oracle's restatement of the reference's CPU path (what the
 reference itself executes: torch CPU ops + autograd), timed on this box's host cores on a bounded
-sample of each workload.  One JSON line per config.  (Config 2's baseline is in bench.py.)"""
+sample of each workload.  One JSON line per config.  (Config 2's baseline is in bench.py --full.)"""
 import json
 import os
 import sys

@@ -17,5 +17,5 @@ done
 cp build/ab/PT.so torchebm_amd/libebm_hip.so
 { python scripts/mlp_phase_times.py 32 128; python scripts/mlp_phase_times.py 2 128; python scripts/mlp_phase_times.py 64 128; } > $O/r03_mlp_phase_times.txt 2>&1
 cp build/ab/CUR.so torchebm_amd/libebm_hip.so
-python bench.py --steps 20 --warmup 3 > $O/r03_bench_n1.json 2> $O/r03_bench_n1.err
+python bench.py --steps 20 --warmup 3 --full > $O/r03_bench_n1.json 2> $O/r03_bench_n1.err
 tail -5 $O/r03_ab_mlp.txt; wc -l $O/r03_*

@@ -42,7 +42,7 @@ with open(os.path.join(dst, f"{tag}_kernel_stats.csv"), "w") as f:
             f"{float(r['MinNs'])/1e6:.4f},{float(r['MaxNs'])/1e6:.4f},{float(r['Percentage']):.3f}\n"
         )
 
-# The default bench.py run also measures the other BASELINE configs (`extra`), some of them with the SAME kernel at
+# bench.py --full also measures the other BASELINE configs (`extra`), some of them with the SAME kernel at
 # another shape (config 4's shard uses the lean chain kernel at dim 128, k 500).  The plain per-name statistics above
 # mix them; this second table splits the package's kernels by launch grid, from the kernel trace.
 trace = os.path.join(src, "trace", "bench_kernel_trace.csv")

@@ -122,11 +122,12 @@ def _free_port():
 
 def test_bench_contract_two_processes_cpu():
     """bench.py launched exactly as the driver does for N > 1 (torch.distributed.run, one process
-    per device), on the CPU plumbing path with gloo: one JSON line from rank 0, aggregate value."""
+    per device), on the CPU plumbing path with gloo: one JSON line from rank 0, aggregate value; with --full, the
+    read-back breakdown."""
     env = dict(os.environ, CUDA_VISIBLE_DEVICES="", OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--device", "cpu", "--n-chains", "256", "--dim", "8", "--k", "3"]
+           "--device", "cpu", "--n-chains", "256", "--dim", "8", "--k", "3", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stderr[-3000:]
@@ -175,7 +176,7 @@ def test_bench_contract_eight_processes_cpu_config4_shape():
     env = dict(os.environ, CUDA_VISIBLE_DEVICES="", OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1",
-           "--device", "cpu", "--config", "4", "--n-chains", "64", "--k", "3"]
+           "--device", "cpu", "--config", "4", "--n-chains", "64", "--k", "3", "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stderr[-3000:]
