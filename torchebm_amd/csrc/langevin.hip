@@ -291,6 +291,15 @@ int launch_langevin_chain_lean(const LangevinChainReq& q, const ChainArgs& a, di
     else hipLaunchKernelGGL((langevin_chain_lean_contracted_kernel<EBM_ENERGY_HARMONIC, C64>), grid, block, 0, st, a);
     return check_launch("ebm_langevin_chain_f32");
   }
+  // the plain DoubleWell call at a power-of-two 4h, b^2 = 1 and sane coefficients: the folded loop (langevin_elem.h FOLD), the same
+  // states bit for bit.  Other DoubleWell parameters keep the literal instantiation below.
+  if (q.e.kind == EBM_ENERGY_DOUBLE_WELL && !q.coef_table && !q.clamp && !q.traj && !ab_switch("EBM_NO_LEAN_FOLD")) {
+    ChainArgs f = a;
+    if (lean_fold_ok(f)) {
+      hipLaunchKernelGGL((langevin_chain_lean_kernel<kDoubleWellFold, false, false, false, false, C64>), grid, block, 0, st, f);
+      return check_launch("ebm_langevin_chain_f32");
+    }
+  }
 #define EBM_LEAN_T(KIND, TB, CL)                                                                                  \
   do {                                                                                                            \
     if (q.traj) hipLaunchKernelGGL((langevin_chain_lean_kernel<KIND, TB, CL, true, false, C64>), grid, block, 0, st, a); \
