@@ -4,7 +4,11 @@ ROUTES pins, for each case, the kernel family the host predicates (csrc/api.hip 
 ``launch_hmc_chain``) send it to: the first and last width of every predicate and the first width past each edge.  The
 inputs, the float64 references and the bars below need no GPU: tests/test_fp64_bars.py checks on the CPU that an fp32
 evaluation meets every bar and that a contraction on two-term bf16 splits fails it; tests/test_fp64_one_step_gpu.py holds
-the kernels to the same bars, tests/test_route_map_gpu.py checks the routes."""
+the kernels to the same bars, tests/test_route_map_gpu.py checks the routes.
+
+The records=True cases run with a diagnostics record buffer attached (that is what selects the records kernels): record_chains
+says which chains the documented geometry puts into which record, record_refs gives every record's float64 references, and
+tests/test_records_fp64_gpu.py reads the records the kernels wrote against them (bars: sums_bar, m2_bar, k_record_energy)."""
 
 import math
 import re
@@ -163,6 +167,10 @@ EDGES = [
     (_key("langevin", "gauss", 201, records=True), _key("langevin", "gauss", 200, records=True)),
     (_key("langevin", "gauss", 64, records=True), _key("langevin", "gauss", 21, records=True)),
     (_key("langevin", "gauss", 200, records=True), _key("langevin", "gauss", 516, records=True, n=200)),
+    (_key("langevin", "gauss", 512, records=True, n=200), _key("langevin", "gauss", 516, records=True, n=200)),
+    (_key("langevin", "gauss", 260, records=True), _key("langevin", "gauss", 260)),
+    (_key("langevin", "gauss", 260, records=True, image=False), _key("langevin", "gauss", 260, image=False)),
+    (_key("langevin", "gauss", 256, records=True, image=False), _key("langevin", "gauss", 260, records=True, image=False)),
     (_key("heun", "gauss", 64), _key("langevin", "gauss", 64)),
     # mixture Langevin
     (_key("langevin", "gmm", 20, K=8), _key("langevin", "gmm", 16, K=8)),
@@ -204,6 +212,7 @@ EDGES = [
     (_key("hmc", "gmm", 252, K=32), _key("hmc", "gmm", 256, K=16)),
     (_key("hmc", "gmm", 254, K=32), _key("hmc", "gmm", 255, K=16)),
     (_key("hmc", "gmm", 132, K=8), _key("hmc", "gmm", 132, K=8, mass="diag")),
+    (_key("hmc", "gmm", 132, K=8), _key("hmc", "gmm", 132, K=8, records=True)),
     (_key("hmc", "gmm", 129, K=16), _key("hmc", "gmm", 132, K=8)),
     (_key("hmc", "gmm", 64, K=33), _key("hmc", "gmm", 32, K=9)),
 ]
@@ -289,6 +298,11 @@ ROUTES = [
     # ---- records: the streamed-Ps forms without the image and on shifted rows, the wide mixtures
     _R('langevin', 'gauss', 256, records=True, image=False, launcher='launch_langevin_chain_gauss_big', family='gauss_big_langevin_kernel<1,true,false>'),
     _R('langevin', 'gauss', 200, records=True, image=False, launcher='launch_langevin_chain_gauss_big', family='gauss_res_langevin_kernel<true,false,false,false>'),
+    # (two slices, above 256 dims: the records instantiation, which the plain call shares only from six out tiles)
+    _R('langevin', 'gauss', 260, records=True, launcher='launch_langevin_chain_gauss_big', family='gauss_big_langevin_kernel<2,true,true>'),
+    _R('langevin', 'gauss', 512, records=True, n=200, launcher='launch_langevin_chain_gauss_big', family='gauss_big_langevin_kernel<2,true,true>'),
+    _R('langevin', 'gauss', 260, records=True, image=False, launcher='launch_langevin_chain_gauss_big', family='gauss_big_langevin_kernel<2,true,false>'),
+    _R('langevin', 'gauss', 384, records=True, image=False, n=200, launcher='launch_langevin_chain_gauss_big', family='gauss_big_langevin_kernel<2,true,false>'),
     _R('langevin', 'gauss', 201, records=True, launcher='launch_langevin_chain_matrix_diag', family='gauss_res_langevin_kernel<true,true,false,true>'),
     _R('langevin', 'gauss', 254, records=True, launcher='launch_langevin_chain_matrix_diag', family='gauss_res_langevin_kernel<true,true,false,true>'),
     _R('langevin', 'gmm', 132, K=12, records=True, launcher='launch_langevin_chain_matrix_diag', family='gmm_wide_langevin_diag_kernel'),
@@ -348,6 +362,8 @@ ROUTES = [
     _R('hmc', 'gmm', 94, K=8, records=True, launcher="launch_hmc_chain_gmm_shift_diag", family="gauss_hmc_mfma_kernel<GmmE,DIAG=true,SH=true>"),
     _R('hmc', 'gmm', 95, K=8, records=True, launcher="launch_hmc_chain", family="hmc_chain_kernel"),
     _R('hmc', 'gmm', 64, K=16, records=True, launcher="launch_hmc_chain_matrix_diag", family="gauss_hmc_mfma_kernel<GmmE,DIAG=true,SH=false>"),
+    # (records of a wide mixture: the matrix-layout records stop at 96 dims, the lane-group kernel writes them)
+    _R('hmc', 'gmm', 132, K=8, records=True, launcher="launch_hmc_chain", family="hmc_chain_kernel"),
     _R('hmc', 'gmm', 132, K=8, launcher="launch_hmc_chain_gmm_wide", family="gauss_hmc_mfma_kernel<GmmE,DIAG=false,SH=false>"),
     _R('hmc', 'gmm', 224, K=16, launcher="launch_hmc_chain_gmm_wide", family="gauss_hmc_mfma_kernel<GmmE,DIAG=false,SH=false>"),
     _R('hmc', 'gmm', 228, K=16, launcher="launch_hmc_chain_gmm_wide", family="gauss_hmc_mfma_kernel<GmmE,DIAG=false,SH=false>"),
@@ -590,18 +606,25 @@ def hmc_ref32(case: Case, x0, p, mass, fp, eps: float):
     return x1
 
 
+def energy64(case: Case, x, fp):
+    """float64 energy of the fp32 parameters and its natural scale N(E), per chain: 1/2 |d|^T |P| |d| for a Gaussian, the
+    expansion scale for a mixture."""
+    x = x.double()
+    if case.energy == "gauss":
+        mean, P = fp
+        d = x - mean.double()
+        return 0.5 * ((d @ P.double().t()) * d).sum(dim=1), 0.5 * ((d.abs() @ P.double().abs().t()) * d.abs()).sum(dim=1)
+    means, sigma, logw = fp
+    return gmm_energy64(x, means, sigma, logw), gmm_energy_scale(x, means, sigma)
+
+
 def hmc_hamiltonians64(case: Case, x0, p, mass, fp, eps: float):
     """float64 H0, H1 of one full leapfrog step (L = 1) and their natural scales N(H0), N(H1)."""
     m = _mass64(mass, case.dim)
     ps = p.double() * m.sqrt()
 
     def energy(x):
-        if case.energy == "gauss":
-            mean, P = fp
-            d = x - mean.double()
-            return 0.5 * ((d @ P.double().t()) * d).sum(dim=1), 0.5 * ((d.abs() @ P.double().abs().t()) * d.abs()).sum(dim=1)
-        means, sigma, logw = fp
-        return gmm_energy64(x, means, sigma, logw), gmm_energy_scale(x, means, sigma)
+        return energy64(case, x, fp)
 
     def grad(x):
         if case.energy == "gauss":
@@ -670,6 +693,198 @@ def hmc_accept_eps(case: Case, x0, p, mass, fp) -> float:
 
 
 # ----------------------------------------------------------------------------------------------------------------
+# Diagnostics records: which chains a record holds, its float64 references and their bars
+# ----------------------------------------------------------------------------------------------------------------
+# The record-to-chain map below restates the documented geometry (include/ebm_hip.h under ebm_diag_layout, the header of
+# csrc/diag.h), not any kernel: a layout is (n_blocks, S, E) as ebm_diag_layout returns it.
+def diag_classes(dim: int) -> int:
+    """K = 4 / gcd(dim, 4) alignment classes of the shifted rows."""
+    return 4 // math.gcd(dim, 4)
+
+
+def record_count(S: int, E: int, n: int, dim: int) -> int:
+    """records per kept step: ceil(n dim / E) blocks of E flat elements; ceil(n / 32 K) K for interleaved classes (E < 0)."""
+    if E < 0:
+        K = diag_classes(dim)
+        return -(-n // (32 * K)) * K
+    return -(-(n * dim) // E)
+
+
+def record_chains(layout, n: int, dim: int):
+    """For every record b, the flat indices (into the row-major [n, dim] state) of the elements it holds, as a [rows, S]
+    tensor: column s of it is what slot s sums.  rows = 0: a record without chains.
+      E < 0            interleaved classes: record b = (group b / K, class b % K) holds chains 32 K g + K m + s, m = 0 .. 31
+      S > dim          packed rows: the state read as n dim / S rows of width S, E / S of them per record
+      E % dim == 0     E / dim whole chains per record
+      dim % E == 0     one slice of E elements of one chain per record (slot s is column (b E) % dim + s)"""
+    nb, S, E = layout
+    cols = torch.arange(S)
+    if E < 0:
+        assert E == -32 * dim and S == dim, layout
+        K = diag_classes(dim)
+        out = []
+        for b in range(nb):
+            g, s = divmod(b, K)
+            chains = 32 * K * g + K * torch.arange(32) + s
+            out.append(chains[chains < n][:, None] * dim + cols[None])
+        return out
+    W = max(S, dim)  # the width of the rows the records speak of
+    total = n * dim
+    assert total % W == 0 and W % dim == 0, layout
+    if E % W == 0:
+        assert S == W, layout
+        per, rows_total = E // W, total // W
+        return [torch.arange(min(b * per, rows_total), min((b + 1) * per, rows_total))[:, None] * W + cols[None] for b in range(nb)]
+    assert W == dim and dim % E == 0 and S == E, layout
+    return [(b * E + cols)[None] if b * E < total else torch.empty(0, S, dtype=torch.long) for b in range(nb)]
+
+
+def record_groups(layout, n: int, dim: int):
+    """[(records, chains)]: the smallest runs of consecutive records that cover whole chains -- one record each, except
+    where a chain is spread over dim / E records: only the sum of their energy and accept shares is defined."""
+    nb, S, E = layout
+    idx = record_chains(layout, n, dim)
+    if 0 < E < dim:
+        per = dim // E
+        return [(list(range(b, b + per)), torch.unique(torch.cat([idx[r].flatten() for r in range(b, b + per)]) // dim))
+                for b in range(0, nb, per)]
+    return [([b], torch.unique(idx[b].flatten() // dim)) for b in range(nb)]
+
+
+def wave_layout(n: int, dim: int):
+    """the layout of a matrix-layout kernel's records, where a wave of 32 rows is the block: interleaved classes for widths
+    off multiples of 4 (shifted rows), S / dim = 2, 4, .. chains packed into one row for Gaussians narrower than 20 (the
+    first packing that is a multiple of 4 from 20 up and divides n: csrc/gauss_mfma.hip gauss_pack_factor)."""
+    if dim >= 20 and dim % 4:
+        return record_count(dim, -32 * dim, n, dim), dim, -32 * dim
+    S = dim
+    while S < 20 or S % 4:
+        S *= 2
+    assert S == dim or (n % (S // dim) == 0 and S <= 128), (n, dim)
+    return record_count(S, 32 * S, n, dim), S, 32 * S
+
+
+def rows_layout(n: int, dim: int, chains: int):
+    """the layout of a lane-group kernel that keeps `chains` chains per workgroup"""
+    return record_count(dim, chains * dim, n, dim), dim, chains * dim
+
+
+# lane-group kernels: their records come from diag::emit, which adds a slot's rows one after the other; every other records
+# family keeps 32 chains in a wave's matrix layout and adds them as a tree of five levels (diag.h half_wave_sum)
+EMIT_FAMILIES = ("langevin_chain_rows_kernel", "langevin_heun_rows_kernel", "langevin_chain_pair_kernel", "hmc_chain_kernel",
+                 "hmc_chain_kernel_w2")
+
+
+def record_depth(case: Case, layout) -> int:
+    """the longest chain of fp32 additions an element passes through on its way into a record's sum"""
+    nb, S, E = layout
+    if case.family in EMIT_FAMILIES:
+        return max(1, E // max(S, case.dim))  # rows per block
+    assert abs(E) == 32 * S, (case.id, layout)
+    return 5
+
+
+def gamma(d: int) -> float:
+    """the bound of d chained fp32 roundings"""
+    return d * U / (1.0 - d * U)
+
+
+def sums_bar(depth: int, abs_sum):
+    """|fl(sum x) - sum x| <= gamma(depth) sum |x|, whatever the order inside that depth"""
+    return gamma(depth) * abs_sum
+
+
+def m2_bar(depth: int, cnt, abs_sum, m2):
+    """Two passes: the centre c = fl(fl(sum) / cnt) (or fl(sum) * fl(1 / cnt): two roundings) is off the mean by at most
+    dmu = (gamma(depth) + 2 U) sum|x| / cnt, and sum (x - c)^2 = M2 + cnt (c - mean)^2 exactly; every term then takes one
+    rounding of x - c (twice in the square), one of the fused multiply-add and `depth` additions."""
+    cnt = cnt.clamp(min=1)
+    shift = cnt * ((gamma(depth) + 2 * U) * abs_sum / cnt).square()
+    return gamma(depth + 3) * (m2 + shift) + shift
+
+
+# The energy share of a record of a wave's 32 chains, in units of U times sum N(E) over its chains.  tests/test_fp64_bars.py
+# (test_record_energy_bars), worst record of each sampled case, n = 300 .. 1000:
+#   Gaussians (10 .. 512 dims, Langevin and HMC with each mass form): the fp32 oracle summed in fp32 0.9 .. 11.4 U (512 dims);
+#   energies from two-term bf16 operands 33 .. 106 U (the lowest: HMC at 200 dims, Langevin at 512 with 39)
+#   mixtures (21 .. 200 dims): the fp32 oracle 0.1 .. 0.5 U, the kernels' expansion |x|^2 - 2 x.mu + |mu|^2 in fp32 0.2 .. 1.4 U
+#   (HMC at 94 dims); two-term operands 2.9 .. 11.4 U (the lowest: Langevin at 200 dims)
+K_REC_GAUSS = 16.0
+K_REC_GMM = 2.0
+
+
+def k_record_energy(case: Case, layout) -> float:
+    """Wave records (32 chains): the measured constants above.  Records of the lane-group kernels hold E / dim chains, down
+    to one, where nothing averages: there a chain's own bar holds.  Its gradient g = P d is good to k_step(dim) U per element
+    of |P||d|, so the products d_i g_i are good to (k_step(dim) + 1) U |d_i| (|P||d|)_i; adding the dim of them as a tree (a
+    lane group's reduction, torch's sum) costs log2(dim) roundings more, adding the record's chains its depth: in all
+    (k_step(dim) + 1 + ceil(log2 dim) + depth) U N(E).  tests/test_fp64_bars.py: the fp32 oracle reaches 29 U at 516 dims on
+    one-chain records (bar 44), 12 U at 260 (bar 43); two-term operands 175 and 233 U.  Mixtures: K_GMM + depth."""
+    if case.family not in EMIT_FAMILIES:
+        return K_REC_GAUSS if case.energy == "gauss" else K_REC_GMM
+    depth = record_depth(case, layout)
+    if case.energy == "gauss":
+        return k_step(case.dim) + 1 + math.ceil(math.log2(case.dim)) + depth
+    return K_GMM + depth
+
+
+@dataclass
+class RecordRefs:
+    cnt: torch.Tensor      # [n_blocks, S] elements per slot
+    sums: torch.Tensor     # [n_blocks, S] float64 column sums
+    abs_sums: torch.Tensor  # ... of |x|: the sums' natural scale
+    m2: torch.Tensor       # [n_blocks, S] sum (x - record mean)^2 about the float64 mean
+    groups: list           # record_groups
+    energy: torch.Tensor   # [groups] float64 energy sum of the group's chains
+    energy_scale: torch.Tensor  # ... of N(E)
+    accepts: torch.Tensor  # [groups] accepted chains
+
+
+def record_refs(layout, n: int, dim: int, x, e64, nat, mask=None, clamp: Optional[float] = None) -> RecordRefs:
+    """float64 references of every record from the state x [n, dim] the kernel itself returned; e64 / nat: energy64 of x;
+    mask: the accept mask of the transition (HMC); clamp: the HMC records' energy clamp (1e10)."""
+    nb, S, E = layout
+    flat = x.double().flatten()
+    cnt, sums, abs_sums, m2 = (torch.zeros(nb, S, dtype=torch.float64) for _ in range(4))
+    for b, idx in enumerate(record_chains(layout, n, dim)):
+        if idx.shape[0] == 0:
+            continue
+        v = flat[idx]
+        cnt[b], sums[b], abs_sums[b] = idx.shape[0], v.sum(dim=0), v.abs().sum(dim=0)
+        m2[b] = (v - v.mean(dim=0, keepdim=True)).square().sum(dim=0)
+    groups = record_groups(layout, n, dim)
+    e = e64 if clamp is None else e64.clamp(-clamp, clamp)
+    energy = torch.stack([e[c].sum() for _, c in groups])
+    scale = torch.stack([nat[c].sum() for _, c in groups])
+    accepts = torch.stack([(mask[c] != 0).sum() if mask is not None else torch.tensor(0) for _, c in groups])
+    return RecordRefs(cnt, sums, abs_sums, m2, groups, energy, scale, accepts)
+
+
+def merge_records64(rec, layout, n: int, dim: int):
+    """The exact merge of raw records [kept, n_blocks, 2 S + 8] in float64 by the pairwise-variance identity, as
+    ebm_diag_finish_f32 documents it: (mean [kept, W], biased var [kept, W] clamped to [1e-10, 1e10] -- zero for a single
+    row --, mean energy [kept], accepted fraction [kept]) over the n dim / W rows of width W = max(S, dim)."""
+    nb, S, E = layout
+    W = max(S, dim)
+    rows = n * dim // W
+    idx = record_chains(layout, n, dim)
+    r = rec.double()
+    kept = r.shape[0]
+    tot, m2 = torch.zeros(kept, W, dtype=torch.float64), torch.zeros(kept, W, dtype=torch.float64)
+    for b in range(nb):
+        if idx[b].shape[0]:
+            tot[:, idx[b][0] % W] += r[:, b, :S]
+    mean = tot / rows
+    for b in range(nb):
+        m = idx[b].shape[0]
+        if m:
+            c = idx[b][0] % W
+            m2[:, c] += r[:, b, S:2 * S] + m * (r[:, b, :S] / m - mean[:, c]).square()
+    var = (m2 / rows).clamp(1e-10, 1e10) if rows > 1 else torch.zeros_like(m2)
+    return mean, var, r[:, :, 2 * S:2 * S + 4].sum(dim=(1, 2)) / rows, r[:, :, 2 * S + 4:2 * S + 8].sum(dim=(1, 2)) / rows
+
+
+# ----------------------------------------------------------------------------------------------------------------
 # Running a case on the GPU
 # ----------------------------------------------------------------------------------------------------------------
 def device_model(case: Case, dev):
@@ -704,52 +919,94 @@ def cpu_params(case: Case):
     return means, sigma, model.log_weights.detach().clone()
 
 
-def _records(case: Case, spec, sampler_code, n, dim, injected, dev):
+@dataclass
+class Run:
+    """what a chain call left behind (CPU tensors): the final state, the accept masks [T, n] (HMC), the trajectory
+    [n, kept, dim], the raw records [kept, n_blocks, 2 S + 8] and their layout (n_blocks, S, E) as ebm_diag_layout gave it."""
+    x: torch.Tensor
+    mask: Optional[torch.Tensor] = None
+    traj: Optional[torch.Tensor] = None
+    rec: Optional[torch.Tensor] = None
+    layout: Optional[Tuple[int, int, int]] = None
+
+
+def _records(case: Case, spec, sampler_code, n, dim, injected, with_traj, kept, records, dev):
     from torchebm_amd import _lib
 
-    if not case.records:
-        return None
-    layout = _lib.diag_layout(spec.to_c(), sampler_code, n, dim, injected, False)
+    if not (case.records if records is None else records):
+        return None, None
+    layout = _lib.diag_layout(spec.to_c(), sampler_code, n, dim, injected, with_traj)
     assert layout is not None, f"{case.id}: no in-kernel records for this shape"
     nb, S, _ = layout
-    return torch.zeros(nb * (2 * S + 8), device=dev)
+    return layout, torch.zeros(max(kept, 1) * nb * (2 * S + 8), device=dev)
 
 
-def run_langevin(case: Case, spec, x0, eta: float, noise_field: bool, dev):
-    """one step (k = 1) through the fused chain entry: noise-free (noise_coef = 0, no noise pointer), or with an injected
-    all-zero noise field and noise_coef != 0 (the kernels that read a noise field)."""
+def _run(x, mask, traj, rec, layout, kept):
+    torch.cuda.synchronize()
+    if rec is not None:
+        rec = rec.cpu().view(max(kept, 1), layout[0], 2 * layout[1] + 8)[:kept]
+    return Run(x.cpu(), None if mask is None else mask.cpu(), None if traj is None else traj.cpu(), rec, layout)
+
+
+def run_langevin(case: Case, spec, x0, eta: float, noise_field: bool, dev, k: int = 1, thin: int = 1, traj: bool = False,
+                 records: Optional[bool] = None) -> Run:
+    """k steps (one by default) through the fused chain entry: noise-free (noise_coef = 0, no noise pointer), or with an
+    injected all-zero noise field and noise_coef != 0 (the kernels that read a noise field).  `records`: attach a record
+    buffer (default: case.records -- that is what selects the records kernels); `traj`: hand over a trajectory pointer."""
     from torchebm_amd import _lib
 
     n, dim = case.n, case.dim
     heun = case.sampler == "heun"
     x = x0.to(dev).clone()
-    noise = torch.zeros(1, n, dim, device=dev) if noise_field else None
-    rec = _records(case, spec, _lib.DIAG_LANGEVIN_HEUN if heun else _lib.DIAG_LANGEVIN, n, dim, noise_field, dev)
+    noise = torch.zeros(k, n, dim, device=dev) if noise_field else None
+    tr = torch.zeros(n, k // thin, dim, device=dev) if traj else None
+    layout, rec = _records(case, spec, _lib.DIAG_LANGEVIN_HEUN if heun else _lib.DIAG_LANGEVIN, n, dim, noise_field, traj, k // thin,
+                           records, dev)
     c = spec.to_c()
-    _lib.call("ebm_langevin_heun_chain_f32" if heun else "ebm_langevin_chain_f32", c, x.data_ptr(), n, dim, 1, eta, eta ** 0.5,
-              1.4142135 if noise_field else 0.0, None, 0, 0.0, 0.0, 1, None, None if rec is None else rec.data_ptr(),
-              None if noise is None else noise.data_ptr(), 3, 0, _lib.stream_handle(dev))
-    torch.cuda.synchronize()
-    return x.cpu()
+    _lib.call("ebm_langevin_heun_chain_f32" if heun else "ebm_langevin_chain_f32", c, x.data_ptr(), n, dim, k, eta, eta ** 0.5,
+              1.4142135 if noise_field else 0.0, None, 0, 0.0, 0.0, thin, None if tr is None else tr.data_ptr(),
+              None if rec is None else rec.data_ptr(), None if noise is None else noise.data_ptr(), 3, 0, _lib.stream_handle(dev))
+    return _run(x, None, tr, rec, layout, k // thin)
 
 
-def run_hmc(case: Case, spec, x0, p, u, mass, eps: float, dev):
-    """one transition (T = 1) of one leapfrog step (L = 1) with injected momenta and uniforms: (x, accept mask)."""
+def run_hmc(case: Case, spec, x0, p, u, mass, eps: float, dev, T: int = 1, L: int = 1, thin: int = 1, traj: bool = False,
+            records: Optional[bool] = None) -> Run:
+    """T transitions (one by default) of L leapfrog steps with injected momenta p [T, n, dim] and uniforms u [T, n]."""
     from torchebm_amd import _lib
 
     n, dim = case.n, case.dim
     x = x0.to(dev).clone()
-    p_d, u_d = p.reshape(1, n, dim).to(dev).contiguous(), u.reshape(1, n).to(dev).contiguous()
-    mask = torch.full((1, n), 7, dtype=torch.uint8, device=dev)
+    p_d, u_d = p.reshape(T, n, dim).to(dev).contiguous(), u.reshape(T, n).to(dev).contiguous()
+    mask = torch.full((T, n), 7, dtype=torch.uint8, device=dev)
+    tr = torch.zeros(n, T // thin, dim, device=dev) if traj else None
     kind, scalar, mdiag = _lib.MASS_NONE, 1.0, None
     if isinstance(mass, float):
         kind, scalar = _lib.MASS_SCALAR, mass
     elif mass is not None:
         kind, mdiag = _lib.MASS_DIAG, mass.to(dev).contiguous()
-    rec = _records(case, spec, _lib.DIAG_HMC, n, dim, True, dev)
+    layout, rec = _records(case, spec, _lib.DIAG_HMC, n, dim, True, traj, T // thin, records, dev)
     c = spec.to_c()
-    _lib.call("ebm_hmc_chain_f32", c, x.data_ptr(), n, dim, 1, 1, eps, None, kind, scalar,
-              None if mdiag is None else mdiag.data_ptr(), 1, None, None if rec is None else rec.data_ptr(), mask.data_ptr(), None,
-              p_d.data_ptr(), u_d.data_ptr(), 3, 0, _lib.stream_handle(dev))
+    _lib.call("ebm_hmc_chain_f32", c, x.data_ptr(), n, dim, T, L, eps, None, kind, scalar,
+              None if mdiag is None else mdiag.data_ptr(), thin, None if tr is None else tr.data_ptr(),
+              None if rec is None else rec.data_ptr(), mask.data_ptr(), None, p_d.data_ptr(), u_d.data_ptr(), 3, 0,
+              _lib.stream_handle(dev))
+    return _run(x, mask, tr, rec, layout, T // thin)
+
+
+def diag_finish(run: Run, n: int, dim: int, dev, accept: bool):
+    """ebm_diag_finish_f32 on the run's records: (mean [kept, W], var [kept, W], energy [kept], accept [kept] | None) with
+    W = max(S, dim) -- packed rows (S > dim) are merged as the n dim / S rows of width S they are (include/ebm_hip.h)."""
+    from torchebm_amd import _lib
+
+    nb, S, E = run.layout
+    kept = run.rec.shape[0]
+    W = max(S, dim)
+    rows = n * dim // W
+    rec = run.rec.to(dev).contiguous()
+    mean, var = torch.zeros(kept, W, device=dev), torch.zeros(kept, W, device=dev)
+    energy, acc = torch.zeros(kept, device=dev), torch.zeros(kept, device=dev)
+    work = torch.zeros(kept * (3 * W + 3), dtype=torch.float64, device=dev)
+    _lib.call("ebm_diag_finish_f32", rec.data_ptr(), kept, nb, S, E, rows, W, mean.data_ptr(), var.data_ptr(), energy.data_ptr(),
+              acc.data_ptr() if accept else None, work.data_ptr(), _lib.stream_handle(dev))
     torch.cuda.synchronize()
-    return x.cpu(), mask.cpu()[0]
+    return mean.cpu(), var.cpu(), energy.cpu(), acc.cpu() if accept else None

@@ -56,7 +56,7 @@ def check_langevin(case, x0, fp, got):
 def test_langevin_step_is_fp32_accurate(cuda_device, case, noise_field):
     _, spec, fp = cc.device_model(case, cuda_device)
     x0 = cc.langevin_x0(case, fp)
-    got = cc.run_langevin(case, spec, x0, langevin_eta(case), noise_field, cuda_device)
+    got = cc.run_langevin(case, spec, x0, langevin_eta(case), noise_field, cuda_device).x
     check_langevin(case, x0, fp, got)
 
 
@@ -72,7 +72,8 @@ def test_hmc_leapfrog_step_is_fp32_accurate(cuda_device, case):
     eps = cc.hmc_eps(case, x0, p, mass, fp, target=1.0 if case.energy == "gauss" else cc.GMM_FORCE_TARGET)
     want, natural, gmax = cc.hmc_ref(case, x0, p, mass, fp, eps)
     assert gmax < 1e5  # the force clamp at 1e6 is not reached
-    got, mask = cc.run_hmc(case, spec, x0, p, torch.zeros(case.n), mass, eps, cuda_device)
+    run = cc.run_hmc(case, spec, x0, p, torch.zeros(case.n), mass, eps, cuda_device)
+    got, mask = run.x, run.mask[0]
     assert bool((mask == 1).all()), "u = 0 accepts every proposal"
     err = (got.double() - want).abs()
     if case.energy == "gauss":
@@ -94,6 +95,6 @@ def test_hmc_accept_decision_resolves_the_fp64_energy(cuda_device, case):
     keep, u, below = cc.accept_draws(h0, h1, n0, n1)
     assert keep.sum().item() >= case.n // 4, keep.sum().item()
     assert (keep & below).any() and (keep & ~below).any()
-    _, mask = cc.run_hmc(case, spec, x0, p, u, mass, eps, cuda_device)
+    mask = cc.run_hmc(case, spec, x0, p, u, mass, eps, cuda_device).mask[0]
     wrong = keep & (mask.bool() != below)
     assert not wrong.any(), (case.id, wrong.nonzero().flatten()[:8].tolist(), int(wrong.sum()))

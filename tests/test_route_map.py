@@ -82,3 +82,16 @@ def test_every_pinned_family_sits_on_a_predicate_edge():
     # (a case's noise-field family comes with its plain one)
     missing = {f for c in cc.ROUTES for f in c.family.split()} - on_edge
     assert not missing, f"pinned families with no case at a predicate edge: {sorted(missing)}"
+
+
+def test_every_records_family_is_pinned_by_a_records_case():
+    """the kernels that write diagnostics records themselves -- a *_diag_kernel, a DIAG=true instantiation of the matrix-core
+    HMC template, a <true, ...> instantiation of the streamed-Ps Langevin kernels -- each have a records=True case, which
+    is what tests/test_records_fp64_gpu.py reads the records of"""
+    def emits(f):
+        return f.endswith("_diag_kernel") or "DIAG=true" in f or re.match(r"gauss_(res|big)_langevin_kernel<(true,|\d+,true,)", f)
+
+    fams = {f for f in library_kernel_families() if emits(f) and f not in cc.KERNELS_OFF_ROUTE}
+    assert len(fams) >= 10, sorted(fams)
+    with_records = {f for c in cc.ROUTES if c.records for f in (c.family + " " + c.family_noise).split()}
+    assert not fams - with_records, f"records-emitting families without a records=True case: {sorted(fams - with_records)}"
