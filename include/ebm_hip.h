@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define EBM_ABI_VERSION 8
+#define EBM_ABI_VERSION 9
 
 #if defined(__GNUC__)
 #define EBM_API __attribute__((visibility("default")))
@@ -73,7 +73,7 @@ enum {
                                  embedded in the first coordinates, e.g. BASELINE config 3's ring) the one-lane-per-chain
                                  kernels (dim 16 / 32, K <= 8) run their K x dim passes over four columns only.
                                  A wrong mask gives wrong samples; NULL is always safe.                                    */
-  EBM_ENERGY_MLP         = 4  /* E = w3 . silu(W2 silu(W1 x + b1) + b2) + b3   (the energy of the reference's
+  EBM_ENERGY_MLP         = 4, /* E = w3 . silu(W2 silu(W1 x + b1) + b2) + b3   (the energy of the reference's
                                  examples/20-training/01-mcmc-losses/02-persistent-cd/main.py:21-31)
                                  n_comp = hidden width H (64 or 128; 256 only in a build made with `make H256=1`), dim <= 128 (the reference's benchmark network
                                  benchmarks/registry.py:372-387 at dim 8 / 32 / 128),
@@ -87,6 +87,17 @@ enum {
                                  three-way split operands (fp32 accuracy) as the narrower shapes always do; without it on
                                  the exact-f32 matrix instruction (1.6x slower).  A stale image gives the old network's
                                  samples; NULL is always safe.                                                            */
+  /* The three test landscapes of the reference's core (since ABI version 9): scalars only, dev0 = dev1 = aux = NULL, n_comp = 0.
+     Lane-group kernels, dim <= 1024 (EBM_EDIM above); taken by ebm_langevin_chain_f32, ebm_langevin_heun_chain_f32,
+     ebm_hmc_chain_f32, ebm_descent_chain_f32, ebm_energy_grad_f32 and ebm_diag_layout, not by ebm_hmc_chain_audit_f32.
+     Tolerance tier: sums run in another order than torch's (docs/design/landscapes.md).                                   */
+  EBM_ENERGY_ROSENBROCK  = 5, /* E = sum_{i<dim-1} (a - x_i)^2 + b (x_{i+1} - x_i^2)^2   base_model.py:232-264
+                                 s[0]=a  s[1]=b;  dim >= 2 (EBM_EDIM below: the reference raises there)                   */
+  EBM_ENERGY_ACKLEY      = 6, /* E = -a exp(-b sqrt(mean_j x_j^2)) - exp(mean_j cos(c x_j)) + a + e   base_model.py:267-294
+                                 s[0]=a  s[1]=b  s[2]=c.  s[2] == (float)(2 pi) evaluates cos / sin(c x) as cospi / sinpi(2 x)
+                                 (no argument product, no range reduction), any other c as cos / sin of the fp32 product.
+                                 The gradient at x = 0 is NaN in every coordinate, as autograd's is (inf * 0).             */
+  EBM_ENERGY_RASTRIGIN   = 7  /* E = a dim + sum_j x_j^2 - a cos(2 pi x_j)               base_model.py:297-316   s[0]=a   */
 };
 
 typedef struct ebm_energy {

@@ -39,6 +39,7 @@ class FusedSpec:
     aux: Optional[torch.Tensor] = None  # device int32 hints (mixture: active-column mask), see include/ebm_hip.h
     elementwise: bool = False  # gradient of coordinate j depends on x_j only
     dim: Optional[int] = None  # the model's own state width (None: any width, e.g. element-wise energies)
+    min_dim: int = 1  # narrowest state the energy is defined on (Rosenbrock: 2)
     langevin_only: bool = False  # fused for Euler-Maruyama Langevin chains, HMC and energy/gradient evaluation; no Heun / descent kernel
     hmc: bool = True  # ebm_hmc_chain_f32 takes this energy at this shape
 
@@ -172,7 +173,8 @@ class HarmonicModel(BaseModel):
 
 class RosenbrockModel(BaseModel):
     r"""``E(x) = \sum_{i<n} b (x_{i+1} - x_i^2)^2 + (a - x_i)^2`` (base_model.py:232-264).  A test landscape of the
-    reference's ``core``; no fused kernel -- the samplers drive it through the autograd step route."""
+    reference's ``core``.  Fused (``EBM_ENERGY_ROSENBROCK``, lane-group kernels with a neighbour exchange along the row) at
+    widths 2 ... 1024; wider states and ``gradient()`` itself stay autograd."""
 
     def __init__(self, a: float = 1.0, b: float = 100.0, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -186,10 +188,16 @@ class RosenbrockModel(BaseModel):
         head, tail = x[:, :-1], x[:, 1:]
         return ((self.a - head).pow(2) + self.b * (tail - head.pow(2)).pow(2)).sum(dim=-1)
 
+    def fused_spec(self) -> Optional[FusedSpec]:
+        if not self._is_exactly(RosenbrockModel):
+            return None
+        return FusedSpec(_lib.ENERGY_ROSENBROCK, (self.a, self.b, 0.0, 0.0), min_dim=2)
+
 
 class AckleyModel(BaseModel):
-    r"""``E(x) = -a e^{-b \sqrt{\overline{x^2}}} - e^{\overline{\cos(c x)}} + a + e`` (base_model.py:267-294); autograd
-    step route."""
+    r"""``E(x) = -a e^{-b \sqrt{\overline{x^2}}} - e^{\overline{\cos(c x)}} + a + e`` (base_model.py:267-294).
+    Fused (``EBM_ENERGY_ACKLEY``) at widths up to 1024; a ``c`` that rounds to ``float32(2 * math.pi)`` takes the kernels' sinpi / cospi form.  The
+    gradient at the origin is NaN in every coordinate on every route, as the reference's autograd gives it."""
 
     def __init__(self, a: float = 20.0, b: float = 0.2, c: float = 2 * math.pi, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -203,9 +211,15 @@ class AckleyModel(BaseModel):
         ripple = -torch.exp(torch.sum(torch.cos(self.c * x), dim=-1) / n)
         return radial + ripple + self.a + math.e
 
+    def fused_spec(self) -> Optional[FusedSpec]:
+        if not self._is_exactly(AckleyModel):
+            return None
+        return FusedSpec(_lib.ENERGY_ACKLEY, (self.a, self.b, self.c, 0.0))
+
 
 class RastriginModel(BaseModel):
-    r"""``E(x) = a n + \sum_j x_j^2 - a \cos(2 \pi x_j)`` (base_model.py:297-316); autograd step route."""
+    r"""``E(x) = a n + \sum_j x_j^2 - a \cos(2 \pi x_j)`` (base_model.py:297-316).  Fused
+    (``EBM_ENERGY_RASTRIGIN``) at widths up to 1024, on the lane-group kernels (``elementwise`` stays ``False``)."""
 
     def __init__(self, a: float = 10.0, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -215,6 +229,11 @@ class RastriginModel(BaseModel):
         if x.ndim == 1:
             x = x.unsqueeze(0)
         return self.a * x.shape[-1] + torch.sum(x**2 - self.a * torch.cos(2 * math.pi * x), dim=-1)
+
+    def fused_spec(self) -> Optional[FusedSpec]:
+        if not self._is_exactly(RastriginModel):
+            return None
+        return FusedSpec(_lib.ENERGY_RASTRIGIN, (self.a, 0.0, 0.0, 0.0))
 
 
 class GaussianModel(BaseModel):
@@ -710,6 +729,7 @@ def fused_spec_for(model, x: torch.Tensor, model_kwargs: Optional[dict], *, cap_
       ``means``, the MLP's ``in_dim``): the kernels index the parameters with ``x.shape[1]``, so a mismatch
       would read them with the wrong stride or out of bounds -- on the step route the model's ``forward``
       raises the reference's ``ValueError`` instead (core/base_model.py:185-188);
+    * a state narrower than the energy is defined on (``RosenbrockModel`` needs two coordinates);
     * rows wider than ``FUSED_MAX_ROW`` for the row-coupled kernels (``cap_elementwise=False`` lifts the cap
       for element-wise energies where the caller uses the flat kernel, which has no row limit);
     * a state that is not ``[n, dim]``: the analytic energies reduce over the last axis only, so for a
@@ -729,6 +749,8 @@ def fused_spec_for(model, x: torch.Tensor, model_kwargs: Optional[dict], *, cap_
         return None
     width = x.shape[1]
     if spec.dim is not None and width != spec.dim:
+        return None
+    if width < spec.min_dim:  # Rosenbrock at width 1: the step route raises the reference's ValueError
         return None
     if width > FUSED_MAX_ROW and (cap_elementwise or not spec.elementwise):
         return None

@@ -95,6 +95,12 @@ int check_energy(const ebm_energy_t* en, int32_t dim, const char* who) {
     case EBM_ENERGY_MLP:
       if (!en->dev0) return fail(EBM_EINVAL, "%s: MLP energy needs the packed parameter pointer", who);
       return 0;
+    case EBM_ENERGY_ROSENBROCK:
+      if (dim < 2) return fail(EBM_EDIM, "%s: the Rosenbrock energy needs at least 2 dimensions (got %d)", who, dim);
+      return 0;
+    case EBM_ENERGY_ACKLEY:
+    case EBM_ENERGY_RASTRIGIN:
+      return 0;
     default:
       return fail(EBM_EKIND, "%s: unknown energy kind %d", who, en->kind);
   }

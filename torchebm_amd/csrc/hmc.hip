@@ -16,11 +16,17 @@ void launch_double_well(const rows::Geometry&, dim3, size_t, hipStream_t, const 
 void launch_harmonic(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
 void launch_gaussian(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
 void launch_gmm(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
+void launch_rosenbrock(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
+void launch_ackley(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
+void launch_rastrigin(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
 // ... and the variants that emit diagnostics records at the kept transitions (hmc_*_diag.hip)
 void launch_double_well_diag(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
 void launch_harmonic_diag(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
 void launch_gaussian_diag(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
 void launch_gmm_diag(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
+void launch_rosenbrock_diag(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
+void launch_ackley_diag(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
+void launch_rastrigin_diag(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
 // hmc_literal.hip: the audit form for the element-wise energies (ebm_hmc_chain_audit_f32)
 void launch_literal_double_well(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
 void launch_literal_harmonic(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
@@ -41,7 +47,8 @@ static bool hmc_geometry(const ebm_energy_t& e, int32_t dim, Geometry& geo) {
   static const int nv_env = ab_int("EBM_HMC_NV");
   // (not (1, 8) for a mixture of more than eight components: with identity mass that geometry exists only as hmc_ring.hip /
   //  hmc_gmm32.hip, which stop at K = 8 -- launch_geo<GMM> would launch nothing and the call would return success: ADVICE r5)
-  if (dim == 32 && (nv_env == 2 || nv_env == 4 || nv_env == 8) && !(nv_env == 8 && e.kind == EBM_ENERGY_GMM && e.n_comp > 8))
+  // (the landscape kinds have no instantiation of the alternatives: hmc_kernel.h launch_geo)
+  if (dim == 32 && e.kind < EBM_ENERGY_ROSENBROCK && (nv_env == 2 || nv_env == 4 || nv_env == 8) && !(nv_env == 8 && e.kind == EBM_ENERGY_GMM && e.n_comp > 8))
     geo = Geometry{8 / nv_env, nv_env, true};
   // measured on MI355X (profiles/r01_bench_kernels.jsonl): the small-mixture energy is fastest with
   // ONE lane per chain -- the means become wave-uniform scalar operands (no LDS traffic, no cross-lane
@@ -172,6 +179,9 @@ int launch_hmc_chain(const HmcChainReq& q, hipStream_t st) {
       case EBM_ENERGY_DOUBLE_WELL: hmc::launch_double_well_diag(geo, grid, smem, st, a); break;
       case EBM_ENERGY_HARMONIC:    hmc::launch_harmonic_diag(geo, grid, smem, st, a); break;
       case EBM_ENERGY_GAUSSIAN:    hmc::launch_gaussian_diag(geo, grid, smem, st, a); break;
+      case EBM_ENERGY_ROSENBROCK:  hmc::launch_rosenbrock_diag(geo, grid, smem, st, a); break;
+      case EBM_ENERGY_ACKLEY:      hmc::launch_ackley_diag(geo, grid, smem, st, a); break;
+      case EBM_ENERGY_RASTRIGIN:   hmc::launch_rastrigin_diag(geo, grid, smem, st, a); break;
       default:                     hmc::launch_gmm_diag(geo, grid, smem, st, a); break;
     }
     return check_launch("ebm_hmc_chain_f32");
@@ -180,6 +190,9 @@ int launch_hmc_chain(const HmcChainReq& q, hipStream_t st) {
     case EBM_ENERGY_DOUBLE_WELL: hmc::launch_double_well(geo, grid, smem, st, a); break;
     case EBM_ENERGY_HARMONIC:    hmc::launch_harmonic(geo, grid, smem, st, a); break;
     case EBM_ENERGY_GAUSSIAN:    hmc::launch_gaussian(geo, grid, smem, st, a); break;
+    case EBM_ENERGY_ROSENBROCK:  hmc::launch_rosenbrock(geo, grid, smem, st, a); break;
+    case EBM_ENERGY_ACKLEY:      hmc::launch_ackley(geo, grid, smem, st, a); break;
+    case EBM_ENERGY_RASTRIGIN:   hmc::launch_rastrigin(geo, grid, smem, st, a); break;
     default:                     hmc::launch_gmm(geo, grid, smem, st, a); break;
   }
   return check_launch("ebm_hmc_chain_f32");

@@ -45,6 +45,8 @@ extern __shared__ __attribute__((aligned(16))) float hmc_smem[];
 //    property "E(x) finite  =>  every x_i and every dE/dx_i is free of NaN, x is finite" (each
 //    coordinate enters E through sums and products only), which turns 2 x 4NV finiteness tests and
 //    4NV NaN-propagating clamps into ONE compare on the group-reduced energy plus v_med3 clamps.
+//    (The landscape energies that break the property -- Ackley: E(0) = 0 with a NaN gradient; Rosenbrock: a product
+//    that overflows in the gradient only -- hand back a check value of their own, rows.h has_grad_check.)
 //    Momentum can still overflow on its own; sum(p_i * 0) is NaN exactly when some p_i is not
 //    finite (packed FMAs).  Lane groups that fail either test take the literal path: NaN-propagating
 //    clamp, scrub, and the force re-evaluation the reference then performs on the scrubbed x.
@@ -100,6 +102,8 @@ __device__ __forceinline__ float leapfrog_steps(const En& en, const LaneT& L, Sl
       } else {
         chk = e = en.template eval<true>(L, x, g);
       }
+    } else if constexpr (has_grad_check<En>::value) {
+      e = en.eval_chk(L, x, g, chk);  // E(x) finite does not vouch for dE/dx here: the body says when it is clean
     } else {
       chk = e = en.template eval<true>(L, x, g);
     }
@@ -578,6 +582,8 @@ void launch_geo(const Geometry& geo, dim3 grid, size_t smem, hipStream_t st, con
       if (geo.G == 4) EBM_HMC_G(4, 4, true);
       else EBM_HMC_G(8, 4, true);
     }
+  } else if constexpr (KIND >= EBM_ENERGY_ROSENBROCK) {
+    // the landscape kinds keep the geometries of pick_geometry: hmc.hip hmc_geometry offers them no dim-32 alternative
   } else if (geo.G == 4 && geo.NV == 2) {  // dim-32 alternatives (full rows only)
     EBM_HMC_G(4, 2, true);
   } else if (geo.G == 2 && geo.NV == 4) {

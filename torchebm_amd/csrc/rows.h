@@ -212,6 +212,7 @@ struct EnergyParams {
   int n_comp;
   int n_comp_pad;     // components staged in LDS (a multiple of 8: rows past n_comp are zero, their log-weight -inf)
   float s0, s1;
+  float s2;           // third scalar (Ackley's c); sits in what was alignment padding, so no other member moves
   const float* dev0;  // global
   const float* dev1;
   int param_in_lds;   // shared parameters were staged into LDS
@@ -250,6 +251,14 @@ struct Smem {
 
 template <int KIND, class LaneT>
 struct Energy;
+
+// An energy whose value can be finite while a component of its gradient is not (Ackley at the origin, a Rosenbrock
+// product that overflows) declares GRAD_CHECK and adds eval_chk(L, x, g, chk): the energy as eval<true> returns it, and
+// in `chk` a group-uniform value that is finite only if the energy and every gradient component are (hmc_kernel.h).
+template <class En, class = void>
+struct has_grad_check { static constexpr bool value = false; };
+template <class En>
+struct has_grad_check<En, decltype((void)En::GRAD_CHECK)> { static constexpr bool value = true; };
 
 template <class LaneT>
 struct Energy<EBM_ENERGY_DOUBLE_WELL, LaneT> {
@@ -993,7 +1002,7 @@ inline bool pick_geometry(int dim, Geometry& geo) {
 // Decide where the shared parameters live and how much dynamic LDS the launch needs.
 inline void plan_params(const ebm_energy_t& e, int dim, const Geometry& geo, EnergyParams& P,
                         int& param_floats, size_t& smem_bytes) {
-  P.kind = e.kind; P.n_comp = e.n_comp; P.s0 = e.s[0]; P.s1 = e.s[1];
+  P.kind = e.kind; P.n_comp = e.n_comp; P.s0 = e.s[0]; P.s1 = e.s[1]; P.s2 = e.s[2];
   P.n_comp_pad = e.n_comp < 8 ? 8 : ((e.n_comp + 7) & ~7);  // whole blocks of eight (see Energy<GMM>::eval_blocks)
   P.dev0 = e.dev0; P.dev1 = e.dev1; P.aux = e.aux;
   P.dim_pad = (dim + 3) & ~3;
@@ -1046,12 +1055,16 @@ inline int64_t blocks_for(int64_t n_chains, const Geometry& geo) {
     }                                                                                            \
   } while (0)
 
+// (the landscape kinds: csrc/landscape_energies.h, which a unit that expands this macro includes after rows.h)
 #define EBM_KIND_LAUNCH(KERNEL, kind, geo, ...)                                                  \
   do {                                                                                           \
     switch (kind) {                                                                              \
       case EBM_ENERGY_DOUBLE_WELL: EBM_GEO_LAUNCH(KERNEL, EBM_ENERGY_DOUBLE_WELL, geo, __VA_ARGS__); break; \
       case EBM_ENERGY_HARMONIC:    EBM_GEO_LAUNCH(KERNEL, EBM_ENERGY_HARMONIC, geo, __VA_ARGS__); break;    \
       case EBM_ENERGY_GAUSSIAN:    EBM_GEO_LAUNCH(KERNEL, EBM_ENERGY_GAUSSIAN, geo, __VA_ARGS__); break;    \
+      case EBM_ENERGY_ROSENBROCK:  EBM_GEO_LAUNCH(KERNEL, EBM_ENERGY_ROSENBROCK, geo, __VA_ARGS__); break;  \
+      case EBM_ENERGY_ACKLEY:      EBM_GEO_LAUNCH(KERNEL, EBM_ENERGY_ACKLEY, geo, __VA_ARGS__); break;      \
+      case EBM_ENERGY_RASTRIGIN:   EBM_GEO_LAUNCH(KERNEL, EBM_ENERGY_RASTRIGIN, geo, __VA_ARGS__); break;   \
       default:                     EBM_GEO_LAUNCH(KERNEL, EBM_ENERGY_GMM, geo, __VA_ARGS__); break;         \
     }                                                                                            \
   } while (0)

@@ -1,9 +1,10 @@
 // k-fused Langevin chain for energies whose gradient couples the coordinates of a chain
-// (Gaussian, Gaussian mixture), and the stand-alone energy / gradient kernel.
+// (Gaussian, Gaussian mixture, the landscapes of landscape_energies.h), and the stand-alone energy / gradient kernel.
 // Layout and energies: rows.h.  Reference: torchebm/samplers/langevin_dynamics.py:154-185,
 // torchebm/core/base_integrator.py:711-731, torchebm/core/base_model.py:181-210.
 #include "chain_launch.h"
 #include "rows.h"
+#include "landscape_energies.h"
 
 namespace ebm {
 using namespace rows;
@@ -436,6 +437,12 @@ int launch_langevin_chain_rows(const LangevinChainReq& q, hipStream_t st) {
     EBM_GEO_LAUNCH(langevin_heun_rows_kernel, EBM_ENERGY_GAUSSIAN, geo, grid, block, smem, st, a);
   else if (heun && e.kind == EBM_ENERGY_GMM)
     EBM_GEO_LAUNCH(langevin_heun_rows_kernel, EBM_ENERGY_GMM, geo, grid, block, smem, st, a);
+  else if (heun && e.kind == EBM_ENERGY_ROSENBROCK)
+    EBM_GEO_LAUNCH(langevin_heun_rows_kernel, EBM_ENERGY_ROSENBROCK, geo, grid, block, smem, st, a);
+  else if (heun && e.kind == EBM_ENERGY_ACKLEY)
+    EBM_GEO_LAUNCH(langevin_heun_rows_kernel, EBM_ENERGY_ACKLEY, geo, grid, block, smem, st, a);
+  else if (heun && e.kind == EBM_ENERGY_RASTRIGIN)  // element-wise, but on the lane-group kernels like the other landscapes
+    EBM_GEO_LAUNCH(langevin_heun_rows_kernel, EBM_ENERGY_RASTRIGIN, geo, grid, block, smem, st, a);
   else if (heun)
     return fail(EBM_EKIND, "ebm_langevin_heun_chain_f32: element-wise energies run on the flat kernel");
   else if (lane_per_chain && dim == 32)
