@@ -275,6 +275,42 @@ EBM_API int ebm_hmc_chain_audit_f32(const ebm_energy_t* energy, float* x, int64_
                                     float* traj, uint8_t* accept_mask, uint32_t* accept_count,
                                     const float* p_noise, const float* u, uint64_t seed, uint64_t offset, void* stream);
 
+/*
+ * Replica-exchange (parallel tempering) Langevin: n_ladders ladders of n_replicas tempered copies of a chain, k_steps
+ * Euler-Maruyama steps of every copy and the swap events between them in ONE launch (an addition to ABI 9: nothing else moved).
+ *
+ * State: x is the SLOT MATRIX [n_ladders * n_replicas, dim], updated in place; row c * R + r is slot r of ladder c, slot 0 the
+ * target.  Slot r runs at temperature T_r (T_0 < T_1 < ...) through the two device arrays noise_coef[R] and beta[R]:
+ * noise_coef[r] = (float)sqrt(2 sigma^2 T_r), beta[r] = (float)(1 / (sigma^2 T_r)), formed in double on the host, rounded once.
+ *
+ * Step s (0 .. k_steps - 1), every slot, the reference's rounding order (as ebm_langevin_chain_f32, nothing contracted):
+ *   x1 = x - eta * g;  dw = xi * sqrt_eta;  x = x1 + noise_coef[r] * dw
+ * xi is the normal field at Philox step step0 + 2 s, addressed by the flat element (c * R + r) * dim + col of the slot matrix.
+ *
+ * Swap event m = (s + 1) / swap_every - 1 follows step s when (s + 1) % swap_every == 0.  Even m pairs the slots (0,1), (2,3), ...,
+ * odd m pairs (1,2), (3,4), ...; unpaired slots do nothing.  For the pair (r, r + 1) of ladder c
+ *   delta = (beta[r] - beta[r + 1]) * (E_r - E_{r+1})        raw fp32 energies of the current states, no clamp
+ * and the two states change slots iff delta == delta and u < exp(min(delta, 0)) (a NaN delta rejects).  u is the uniform field
+ * (what ebm_noise_fill_f32 materialises with EBM_NOISE_UNIFORM, the field the HMC accept step reads) at Philox step
+ * step0 + 2 s + 1, element c * R + r: the lower slot's row.  A call consumes the Philox steps step0 .. step0 + 2 k_steps - 1.
+ *
+ * After step s and its swap event, slot 0's state goes to traj[c, (s + 1) / thin - 1] whenever (s + 1) % thin == 0
+ * (traj: [n_ladders, k_steps / thin, dim], or NULL).
+ * swap_counts: NULL, or device uint32[2 * (R - 1)] that the call ADDS to (zero it first): attempts of the pair (p, p + 1) at
+ * index p, accepted swaps at index R - 1 + p.
+ * noise / u: both NULL (native draws), or the injected fields noise[k_steps, n_ladders * R, dim] and u[n_events, n_ladders * R]
+ * (n_events = k_steps / swap_every; only the lower-slot entries of u are read).
+ *
+ * Lane-group kernels (one lane group per replica, a ladder inside one workgroup, swaps relabel the replicas and move no state):
+ * every analytic energy except EBM_ENERGY_MLP (EBM_EKIND), dim <= 1024 (EBM_EDIM), 2 <= n_replicas <= 64 and
+ * n_replicas * G <= 256 with G = the lanes per row, the power of two >= ceil(dim / 4), at most 64 (EBM_EDIM otherwise).
+ * swap_every >= 1, thin >= 1.  Constant eta only; no diagnostics records.
+ */
+EBM_API int ebm_tempering_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_ladders, int32_t n_replicas, int32_t dim,
+                                    int32_t k_steps, float eta, float sqrt_eta, const float* noise_coef, const float* beta,
+                                    int32_t swap_every, int32_t thin, float* traj, uint32_t* swap_counts, const float* noise,
+                                    const float* u, uint64_t seed, uint64_t step0, void* stream);
+
 /* The accept step with the RNG coordinates in DEVICE memory (rng_state = {seed, step}; the uniforms
  * are drawn at step rng_state[1] + step_delta): the graph-capturable form, see
  * ebm_langevin_step_dev_f32.  No injected-uniform form. */

@@ -1,0 +1,62 @@
+#!/usr/bin/env python3
+"""Replica-exchange Langevin beside plain Langevin on the same rows: 2^16 ladders x 4 slots x dim 32 (the double well, and the
+eight-mode ring mixture of BASELINE config 3), k = 200, a swap event every 10 steps, against LangevinDynamics.sample on
+[2^18, 32] for 200 steps.  Times are event pairs around the one launch of each call (_lib.timed_events), the two samplers
+alternating inside one process; one JSON line per energy is appended to profiles/tempering_bench.jsonl."""
+import json, os, sys, torch
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torchebm_amd as ta
+from torchebm_amd import _lib
+
+dev = torch.device("cuda")
+LADDERS, R, DIM, K, SWAP_EVERY, REPS, WARM = 1 << 16, 4, 32, 200, 10, 10, 2
+small = "--small" in sys.argv  # a rehearsal size
+if small:
+    LADDERS, REPS = 1 << 10, 3
+
+
+def median(v):
+    return sorted(v)[len(v) // 2]
+
+
+def run(name, model):
+    rows = torch.randn(LADDERS * R, DIM, device=dev)
+    pt = ta.ReplicaExchangeLangevin(model, step_size=0.01, temperatures=(1.0, 2.0, 4.0, 8.0), swap_every=SWAP_EVERY, device=dev)
+    ld = ta.LangevinDynamics(model, step_size=0.01, device=dev)
+    ladders = rows.view(LADDERS, R, DIM)
+    acc = None
+    for i in range(WARM + REPS):
+        if i == WARM:
+            torch.cuda.synchronize()
+            _lib.timed_events["ebm_tempering_chain_f32"] = []
+            _lib.timed_events["ebm_langevin_chain_f32"] = []
+        if i == WARM + REPS - 1:
+            _, diag = pt.sample(x=ladders, n_steps=K, return_replicas=True, return_diagnostics=True)
+            acc = diag["swap_acceptance"].tolist()
+        else:
+            pt.sample(x=ladders, n_steps=K, return_replicas=True)
+        ld.sample(x=rows, n_steps=K)
+    torch.cuda.synchronize()
+    t_pt = [a.elapsed_time(b) for a, b in _lib.timed_events.pop("ebm_tempering_chain_f32")]
+    t_ld = [a.elapsed_time(b) for a, b in _lib.timed_events.pop("ebm_langevin_chain_f32")]
+    rec = {
+        "config": f"{name}: {LADDERS} ladders x {R} slots x dim {DIM}, k = {K}, swap_every = {SWAP_EVERY}",
+        "tempering_ms": median(t_pt), "tempering_ms_min": min(t_pt), "tempering_ms_max": max(t_pt),
+        "langevin_ms": median(t_ld), "langevin_ms_min": min(t_ld), "langevin_ms_max": max(t_ld),
+        "ratio_tempering_over_langevin": median(t_pt) / median(t_ld),
+        "row_steps_per_s_tempering": LADDERS * R * K / median(t_pt) * 1e3,
+        "row_steps_per_s_langevin": LADDERS * R * K / median(t_ld) * 1e3,
+        "swap_acceptance": acc, "reps": REPS, "device": torch.cuda.get_device_name(0),
+    }
+    print(json.dumps(rec))
+    return rec
+
+
+if __name__ == "__main__":
+    recs = [run("double well", ta.DoubleWellModel(device=dev)), run("ring_mixture(8, 32)", ta.core.ring_mixture(8, DIM, device=dev))]
+    out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "tempering_bench.jsonl")
+    if not small:
+        with open(out, "a") as f:
+            for r in recs:
+                f.write(json.dumps(r) + "\n")

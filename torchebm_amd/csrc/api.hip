@@ -358,6 +358,30 @@ int ebm_hmc_chain_audit_f32(const ebm_energy_t* energy, float* x, int64_t n_chai
                         mass_scalar, mass_diag, thin, traj, nullptr, accept_mask, accept_count, p_noise, u, seed, offset, stream);
 }
 
+int ebm_tempering_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_ladders, int32_t n_replicas, int32_t dim,
+                            int32_t k_steps, float eta, float sqrt_eta, const float* noise_coef, const float* beta,
+                            int32_t swap_every, int32_t thin, float* traj, uint32_t* swap_counts, const float* noise,
+                            const float* u, uint64_t seed, uint64_t step0, void* stream) {
+  const char* who = "ebm_tempering_chain_f32";
+  if (energy && energy->kind == EBM_ENERGY_MLP)
+    return fail(EBM_EKIND, "%s: the MLP energy has no replica-exchange kernel (the sampler's eager route takes it)", who);
+  if (int r = check_energy(energy, dim, who)) return r;
+  if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
+  if (n_replicas < 2 || n_replicas > 64) return fail(EBM_EINVAL, "%s: n_replicas=%d (a ladder has 2 .. 64 slots)", who, n_replicas);
+  if (n_ladders < 0 || dim < 1) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d, %d]", who, (long long)n_ladders, n_replicas, dim);
+  if (!aligned16(x)) return fail(EBM_EINVAL, "%s: state pointer must be 16-byte aligned", who);
+  if (k_steps < 0 || swap_every < 1 || thin < 1)
+    return fail(EBM_EINVAL, "%s: k_steps=%d swap_every=%d thin=%d", who, k_steps, swap_every, thin);
+  if (int r = tempering_check_geometry(n_replicas, dim)) return r;
+  if (!noise_coef || !beta) return fail(EBM_EINVAL, "%s: noise_coef / beta is NULL", who);
+  if ((noise == nullptr) != (u == nullptr)) return fail(EBM_EINVAL, "%s: noise and u must be given together", who);
+  if (n_ladders == 0 || k_steps == 0) return 0;
+  if ((traj && !aligned16(traj)) || (noise && !aligned16(noise))) return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  const TemperingChainReq q{*energy, x, n_ladders, n_replicas, dim, k_steps, eta, sqrt_eta, noise_coef, beta, swap_every, thin,
+                            traj, swap_counts, noise, u, seed, step0};
+  return tempering_chain_launch(q, (hipStream_t)stream);
+}
+
 int ebm_leapfrog_kick_drift_f32(const float* x, const float* p, const float* force, float* x_new,
                                 float* p_half, int64_t n_chains, int32_t dim, float eps,
                                 int32_t mass_kind, double mass_scalar, const float* mass_diag,

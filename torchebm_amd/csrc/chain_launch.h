@@ -53,6 +53,25 @@ struct HmcChainReq {
   int32_t n_kept() const { return n_mh / thin; }
 };
 
+struct TemperingChainReq {
+  const ebm_energy_t& e;
+  float* x;                 // the slot matrix [n_ladders * n_replicas, dim]
+  int64_t n_ladders;
+  int32_t n_replicas, dim, k_steps;
+  float eta, sqrt_eta;
+  const float* noise_coef;  // device [n_replicas]
+  const float* beta;        // device [n_replicas]
+  int32_t swap_every, thin;
+  float* traj;
+  uint32_t* swap_counts;
+  const float* noise;
+  const float* u;
+  uint64_t seed, offset;
+
+  RngKey key() const { return RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)}; }
+  int32_t n_kept() const { return k_steps / thin; }
+};
+
 // The fields the row-major Langevin argument structs share (GaussArgs, BigArgs, RowChainArgs, WideArgs).
 template <class Args>
 inline void fill_langevin(Args& a, const LangevinChainReq& q) {
@@ -143,5 +162,11 @@ bool gmm_hmc_wide_supported(int32_t dim, int32_t n_comp, int32_t mass_kind);
 bool gmm_hmc_wide_shift_supported(int32_t dim, int32_t n_comp, int32_t mass_kind);
 int launch_hmc_chain_matrix_diag(const HmcChainReq&, hipStream_t);  // matrix_hmc_diag.hip: records of the matrix layout
 bool matrix_hmc_diag_plan(const ebm_energy_t&, int64_t n_chains, int32_t dim, diag::DiagArgs&);
+
+// ---------------------------------------------------------------------------------
+// Replica-exchange Langevin (tempering.hip: a ladder of tempered walkers per chain, swaps inside the launch)
+// ---------------------------------------------------------------------------------
+int tempering_chain_launch(const TemperingChainReq&, hipStream_t);
+int tempering_check_geometry(int32_t n_replicas, int32_t dim);  // 0, or the refusal (dim > 1024, ladder wider than a workgroup)
 
 }  // namespace ebm

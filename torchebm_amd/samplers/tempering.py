@@ -1,0 +1,274 @@
+r"""Replica-exchange (parallel tempering) Langevin dynamics.
+
+Every chain becomes a *ladder* of ``R`` copies at temperatures ``T_0 < T_1 < ... < T_{R-1}``; slot 0 is the target.
+Slot ``r`` takes the Euler-Maruyama step of :class:`LangevinDynamics` with the noise coefficient
+``sqrt(2 sigma^2 T_r)`` -- it samples ``exp(-E / (sigma^2 T_r))`` -- and every ``swap_every`` steps adjacent slots
+propose to exchange their states, accepted with probability ``min(1, exp((beta_r - beta_{r+1}) (E_r - E_{r+1})))``,
+``beta_r = 1 / (sigma^2 T_r)``.  Even events pair the slots (0,1), (2,3), ..., odd events (1,2), (3,4), ....  The hot
+slots cross barriers that the target slot does not, and the swaps carry those crossings down the ladder.
+
+Two execution routes, chosen once per ``sample()`` call (``_route``):
+
+``fused``  CUDA fp32 state, one of the analytic energies (not the MLP), float step size and noise scale, and a ladder
+           that fits one workgroup (``R * G <= 256``, ``G`` the lanes per row): the whole call -- steps, swap events,
+           Philox draws, thinned trajectory of slot 0, swap counters -- is ONE launch of ``ebm_tempering_chain_f32``
+           (include/ebm_hip.h states the algorithm exactly; docs/design/tempering.md the kernel).
+``eager``  everything else (CPU, any other ``BaseModel`` such as ``MLPEnergy`` or a hand-written energy, schedulers): the
+           same algorithm in torch ops, drawing ``randn(n, R, dim)`` per step and ``rand(n, R)`` per event.
+
+A fused-eligible call never falls back to eager: a missing library or a failing launch raises.
+"""
+
+from __future__ import annotations
+
+from typing import Dict, Optional, Sequence, Tuple, Union
+
+import torch
+
+from .. import _lib, _rng
+from ..core.energies import BaseModel, FusedSpec, fused_spec_for
+from ..core.sampler_base import BaseSampler
+from ..core.schedules import BaseScheduler
+
+
+def ladder_coefficients(noise_scale: float, temperatures: Sequence[float]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``(noise_coef[R], beta[R])`` as fp32: formed in double, rounded once (include/ebm_hip.h)."""
+    t = torch.tensor([float(v) for v in temperatures], dtype=torch.float64)
+    s2 = float(noise_scale) ** 2
+    return torch.sqrt(2.0 * s2 * t).to(torch.float32), (1.0 / (s2 * t)).to(torch.float32)
+
+
+def lanes_per_row(dim: int) -> int:
+    """The lane-group width ``G`` of csrc/rows.h (``pick_geometry``) for a row of ``dim`` columns."""
+    nvec = (dim + 3) // 4
+    g = 1
+    while g < nvec and g < 64:
+        g <<= 1
+    return g
+
+
+class ReplicaExchangeLangevin(BaseSampler):
+    """Langevin dynamics on a temperature ladder with replica exchange.
+
+    Args:
+        model: energy model to sample from.
+        step_size: step size, a float or (eager route) a ``BaseScheduler``.
+        noise_scale: noise scale ``sigma`` of the target slot, a float or (eager route) a ``BaseScheduler``.
+        temperatures: strictly increasing, positive, at least two; the first is the target's.
+        swap_every: a swap event follows every ``swap_every``-th step.
+        dtype, device: where the ladders live.
+    """
+
+    def __init__(
+        self,
+        model: BaseModel,
+        step_size: Union[float, BaseScheduler] = 1e-3,
+        noise_scale: Union[float, BaseScheduler] = 1.0,
+        temperatures: Sequence[float] = (1.0, 2.0, 4.0, 8.0),
+        swap_every: int = 10,
+        dtype: torch.dtype = torch.float32,
+        device: Optional[Union[str, torch.device]] = None,
+    ):
+        super().__init__(model=model, dtype=dtype, device=device)
+        self._register_param("step_size", step_size, positive=True)
+        self._register_param("noise_scale", noise_scale, positive=True)
+        temps = tuple(float(t) for t in temperatures)
+        if len(temps) < 2:
+            raise ValueError("temperatures must hold at least two values")
+        if temps[0] <= 0 or any(b <= a for a, b in zip(temps, temps[1:])):
+            raise ValueError(f"temperatures must be positive and strictly increasing, got {temps}")
+        if int(swap_every) < 1:
+            raise ValueError("swap_every must be >= 1")
+        self.temperatures = temps
+        self.swap_every = int(swap_every)
+
+    @property
+    def n_replicas(self) -> int:
+        return len(self.temperatures)
+
+    # ---------------------------------------------------------------------------------
+    # routing: decided here and nowhere else
+    # ---------------------------------------------------------------------------------
+    def _route(self, x: torch.Tensor) -> Tuple[str, Optional[FusedSpec]]:
+        """``x``: the ladders ``[n, R, dim]``."""
+        if not x.is_cuda or x.dtype != torch.float32 or x.ndim != 3:
+            return "eager", None
+        if not (self.schedulers["step_size"].is_constant() and self.schedulers["noise_scale"].is_constant()):
+            return "eager", None
+        if self.use_mixed_precision and self.autocast_available:
+            return "eager", None
+        rows = x.view(-1, x.shape[-1])
+        spec = fused_spec_for(self.model, rows, None)
+        if spec is None or spec.kind == _lib.ENERGY_MLP:
+            return "eager", None
+        if self.n_replicas > 64 or self.n_replicas * lanes_per_row(rows.shape[1]) > 256:
+            return "eager", None
+        return "fused", spec
+
+    # ---------------------------------------------------------------------------------
+    # public API
+    # ---------------------------------------------------------------------------------
+    @torch.no_grad()
+    def sample(
+        self,
+        x: Optional[torch.Tensor] = None,
+        dim: Optional[int] = None,
+        n_steps: int = 100,
+        n_samples: int = 1,
+        thin: int = 1,
+        return_trajectory: bool = False,
+        return_diagnostics: bool = False,
+        return_replicas: bool = False,
+        generator: Optional[torch.Generator] = None,
+    ) -> Union[torch.Tensor, Tuple[torch.Tensor, Dict[str, torch.Tensor]]]:
+        """Run ``n_steps`` steps of every slot with the swap events between them.
+
+        ``x``: ``[n, dim]`` (every slot of ladder ``i`` starts at ``x[i]``), ``[n, R, dim]`` (a ladder as
+        ``return_replicas=True`` returned it: continue), or ``None`` (``n_samples`` draws from N(0, I) of width ``dim``).
+
+        Returns the slot-0 states ``[n, dim]``; with ``return_trajectory`` the kept slot-0 states
+        ``[n, n_steps // thin, dim]``; with ``return_replicas`` the whole ladders ``[n, R, dim]``.  With
+        ``return_diagnostics`` a second value: ``"swap_acceptance"`` ``[R - 1]`` (accepted / attempted swaps of each adjacent
+        pair over the call, NaN for a pair that was never attempted) and ``"mean"`` / ``"var"`` (``[n_kept, dim]``, biased
+        variance clamped to [1e-10, 1e10]) / ``"energy"`` (``[n_kept]``) of slot 0 at the kept steps.
+
+        Raises:
+            ValueError: ``thin < 1``, ``x`` and ``dim`` both ``None``, a state that is neither ``[n, dim]`` nor
+                ``[n, R, dim]``, or ``return_trajectory`` together with ``return_replicas``.
+        """
+        if thin < 1:
+            raise ValueError("thin must be >= 1")
+        if return_trajectory and return_replicas:
+            raise ValueError("return_trajectory and return_replicas exclude each other")
+        self.reset_schedulers()
+        R = self.n_replicas
+        x = self._init_state(x, dim, n_samples, generator)
+        if x.ndim == 2:
+            x = x.unsqueeze(1).expand(-1, R, -1)
+        elif x.ndim != 3 or x.shape[1] != R:
+            raise ValueError(f"x must be [n, dim] or [n, {R}, dim], got {tuple(x.shape)}")
+        x = x.contiguous()
+        route, spec = self._route(x)
+        if route == "fused":
+            state, traj, diag = self._sample_fused(x, spec, n_steps, thin, return_trajectory, return_diagnostics, generator)
+        else:
+            state, traj, diag = self._sample_eager(x, n_steps, thin, return_trajectory, return_diagnostics, generator)
+        out = traj if return_trajectory else (state if return_replicas else state[:, 0].contiguous())
+        return (out, diag) if return_diagnostics else out
+
+    # ---------------------------------------------------------------------------------
+    # route: torch ops
+    # ---------------------------------------------------------------------------------
+    def _sample_eager(self, x, n_steps, thin, want_traj, want_diag, generator):
+        n, R, dim = x.shape
+        n_kept = n_steps // thin
+        x = x.clone()
+        traj = torch.empty(n, n_kept, dim, dtype=x.dtype, device=x.device) if want_traj else None
+        diag = self._new_diag(n_kept, dim, x) if want_diag else None
+        tried = torch.zeros(R - 1, dtype=torch.float64)
+        took = torch.zeros(R - 1, dtype=torch.float64)
+        keep = event = 0
+        with self.autocast_context():
+            for s in range(n_steps):
+                eta = self.get_scheduled_value("step_size")
+                coef, beta = ladder_coefficients(self.get_scheduled_value("noise_scale"), self.temperatures)
+                coef, beta = coef.to(x.device, x.dtype).view(1, R, 1), beta.to(x.device, x.dtype)
+                noise = torch.randn(n, R, dim, dtype=x.dtype, device=x.device, generator=generator)
+                grad = self._model_gradient(x.view(n * R, dim), {}).view(n, R, dim)
+                # the reference's Euler-Maruyama op order (LangevinDynamics): rounded mul, rounded add
+                x = (x - eta * grad) + coef * (noise * eta**0.5)
+                self.step_schedulers()
+                if (s + 1) % self.swap_every == 0:
+                    u = torch.rand(n, R, dtype=x.dtype, device=x.device, generator=generator)
+                    energy = self._model_energy(x.view(n * R, dim), {}).view(n, R)
+                    for r in range(event % 2, R - 1, 2):
+                        delta = (beta[r] - beta[r + 1]) * (energy[:, r] - energy[:, r + 1])
+                        ok = (delta == delta) & (u[:, r] < torch.exp(delta.clamp(max=0.0)))
+                        tried[r] += n
+                        took[r] += int(ok.sum())
+                        lower = x[:, r].clone()
+                        x[:, r] = torch.where(ok[:, None], x[:, r + 1], lower)
+                        x[:, r + 1] = torch.where(ok[:, None], lower, x[:, r + 1])
+                    event += 1
+                if (s + 1) % thin == 0:
+                    cold = x[:, 0]
+                    if traj is not None:
+                        traj[:, keep] = cold
+                    if diag is not None:
+                        if n > 1:
+                            diag["mean"][keep] = cold.mean(dim=0)
+                            diag["var"][keep] = cold.var(dim=0, unbiased=False).clamp_(min=1e-10, max=1e10)
+                        else:
+                            diag["mean"][keep] = cold.squeeze(0)
+                            diag["var"][keep].zero_()
+                        diag["energy"][keep] = self._model_energy(cold.contiguous(), {}).mean()
+                    keep += 1
+        if diag is not None:
+            diag["swap_acceptance"] = (took / tried).to(device=x.device, dtype=x.dtype)
+        return x, traj, diag
+
+    def _new_diag(self, n_kept: int, dim: int, like: torch.Tensor) -> Dict[str, torch.Tensor]:
+        return {
+            "mean": torch.empty(n_kept, dim, dtype=like.dtype, device=like.device),
+            "var": torch.empty(n_kept, dim, dtype=like.dtype, device=like.device),
+            "energy": torch.empty(n_kept, dtype=like.dtype, device=like.device),
+        }
+
+    # ---------------------------------------------------------------------------------
+    # route: one launch of ebm_tempering_chain_f32
+    # ---------------------------------------------------------------------------------
+    def _ladder_on(self, device: torch.device, sigma: float) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The two device arrays of the ladder, kept for the next call with the same noise scale."""
+        key = (device, sigma, self.temperatures)
+        cached = getattr(self, "_ladder_cache", None)
+        if cached is None or cached[0] != key:
+            coef, beta = ladder_coefficients(sigma, self.temperatures)
+            cached = (key, coef.to(device), beta.to(device))
+            self._ladder_cache = cached
+        return cached[1], cached[2]
+
+    def _sample_fused(self, x, spec: FusedSpec, n_steps, thin, want_traj, want_diag, generator):
+        n, R, dim = x.shape
+        n_kept = n_steps // thin
+        state = _lib.dense_f32(x).clone()  # the kernel updates in place; never the caller's tensor
+        eta = self.get_scheduled_value("step_size")
+        coef, beta = self._ladder_on(x.device, self.get_scheduled_value("noise_scale"))
+        need_kept = (want_traj or want_diag) and n_kept > 0
+        traj = torch.empty(n, n_kept, dim, dtype=torch.float32, device=x.device) if (want_traj or need_kept) else None
+        counts = torch.zeros(2 * (R - 1), dtype=torch.int32, device=x.device) if want_diag else None
+        seed, step0 = _rng.reserve(generator, x.device, 2 * n_steps)
+        stream = _lib.stream_handle(x.device)
+        spec_c = spec.to_c()
+        if n > 0 and n_steps > 0:
+            _lib.call(
+                "ebm_tempering_chain_f32",
+                spec_c, _lib.ptr(state), n, R, dim, n_steps, eta, eta**0.5, _lib.ptr(coef), _lib.ptr(beta),
+                self.swap_every, thin, _lib.ptr(traj) if need_kept else None, _lib.ptr(counts), None, None, seed, step0, stream,
+            )
+        self.advance_schedulers(n_steps)
+        diag = None
+        if want_diag:
+            diag = self._new_diag(n_kept, dim, state)
+            if n > 0 and n_kept > 0:
+                self._kept_statistics(spec_c, traj, diag, stream)
+            c = (counts.to(torch.int64) & 0xFFFFFFFF).to(torch.float64)  # (uint32 counters in an int32 tensor)
+            diag["swap_acceptance"] = (c[R - 1 :] / c[: R - 1]).to(torch.float32)
+        return state, (traj if want_traj else None), diag
+
+    def _kept_statistics(self, spec_c, traj: torch.Tensor, diag: Dict[str, torch.Tensor], stream) -> None:
+        """mean / var / energy of slot 0 from the kept states, with the column-statistics and energy kernels."""
+        n, n_kept, dim = traj.shape
+        kept = traj.transpose(0, 1).contiguous()  # [n_kept, n, dim]: one dense population per kept step
+        energy = torch.empty(n_kept, n, dtype=torch.float32, device=traj.device)
+        _lib.call("ebm_energy_grad_f32", spec_c, _lib.ptr(kept), n_kept * n, dim, _lib.ptr(energy), None, stream)
+        diag["energy"].copy_(energy.mean(dim=1))
+        if n == 1:
+            diag["mean"].copy_(kept[:, 0])
+            diag["var"].zero_()
+            return
+        work = torch.zeros(2 * dim + 1, dtype=torch.float64, device=traj.device)  # the kernel leaves it zeroed
+        for keep in range(n_kept):
+            _lib.call(
+                "ebm_chain_stats_f32",
+                _lib.ptr(_lib.dense_f32(kept[keep])), n, dim, _lib.ptr(diag["mean"][keep]), _lib.ptr(diag["var"][keep]), _lib.ptr(work), stream,
+            )
