@@ -193,6 +193,26 @@ EBM_API int ebm_langevin_chain_f32(const ebm_energy_t* energy, float* x, int64_t
                            uint64_t seed, uint64_t offset, void* stream);
 
 /*
+ * ebm_langevin_chain_f32 out of place: the chains start from `x_src` and their final state is stored to `x`; `x_src` is only
+ * read.  Every other argument, every result (x, traj, diag_partials) and every error is that of ebm_langevin_chain_f32
+ * called on a copy of x_src -- the same states bit for bit, for every energy -- without the copy where the kernel allows it:
+ * the element-wise kernels (EBM_ENERGY_DOUBLE_WELL, EBM_ENERGY_HARMONIC on the flat layout) load x_src once and store x
+ * once; for every other kernel family the entry copies x_src into x on `stream` first and continues in place.
+ *   x_src        [n_chains, dim]    read-only, 16-byte aligned; NULL or x itself: the in-place call (identical to
+ *                                   ebm_langevin_chain_f32)
+ *   x            [n_chains, dim]    out (in/out when x_src is NULL or x)
+ * The two ranges must be the same or disjoint: any other overlap returns EBM_EINVAL before anything is launched.  With
+ * k_steps == 0, x receives x_src.  An injected `noise` is allowed with a distinct x_src.  A call cut into several launches
+ * (records of a long run) passes x_src to the first launch only and continues in place on x.  Same ABI version: no
+ * existing signature or struct changes.
+ */
+EBM_API int ebm_langevin_chain_from_f32(const ebm_energy_t* energy, const float* x_src, float* x, int64_t n_chains, int32_t dim,
+                           int32_t k_steps, float eta, float sqrt_eta, float noise_coef,
+                           const float* coef_table, int32_t clamp_on, float cmin, float cmax,
+                           int32_t thin, float* traj, float* diag_partials, const float* noise,
+                           uint64_t seed, uint64_t offset, void* stream);
+
+/*
  * The same k fused steps with the reference's Heun (improved Euler) drift update,
  * LangevinDynamics(integrator="heun"): tableau a = ((), (1,)), b = (1/2, 1/2) (integrators/heun.py)
  * evaluated in the op order of BaseSDERungeKuttaIntegrator (core/base_integrator.py:387-397, 711-731):

@@ -36,6 +36,7 @@ EXPORTS = (
     "ebm_langevin_step_diffusion_f32",
     "ebm_langevin_step_dev_f32",
     "ebm_langevin_chain_f32",
+    "ebm_langevin_chain_from_f32",
     "ebm_langevin_heun_chain_f32",
     "ebm_hmc_chain_f32",
     "ebm_hmc_chain_audit_f32",
@@ -78,6 +79,13 @@ EXPORTS = (
 #: prove that a GPU test really went through the HIP library)
 call_counts: Counter = Counter()
 
+#: Entry points that ``call_counts`` and ``timed_events`` book under another entry's name.  ``ebm_langevin_chain_from_f32`` is
+#: the launch of ``ebm_langevin_chain_f32`` -- the same kernels, the same arguments, the same states -- that reads its start
+#: state from a second pointer; the name ``ebm_langevin_chain_f32`` is what the benchmark's kernel timing, the profiling
+#: scripts and the tests' launch counts key on, so the sampler's switch to the out-of-place entry must not hide the launch
+#: from any of them.  Error messages keep the entry's own name.
+BOOKED_AS = {"ebm_langevin_chain_from_f32": "ebm_langevin_chain_f32"}
+
 
 class EnergyDesc(C.Structure):
     """Mirror of ``ebm_energy_t``."""
@@ -104,6 +112,10 @@ _PROTOTYPES = {
     "ebm_langevin_chain_f32": (
         C.c_int,
         [_ENERGY_P, _p, _i64, _i32, _i32, _f, _f, _f, _p, _i32, _f, _f, _i32, _p, _p, _p, _u64, _u64, _p],
+    ),
+    "ebm_langevin_chain_from_f32": (  # ... with `const float* x_src` before `x`
+        C.c_int,
+        [_ENERGY_P, _p, _p, _i64, _i32, _i32, _f, _f, _f, _p, _i32, _f, _f, _i32, _p, _p, _p, _u64, _u64, _p],
     ),
     "ebm_langevin_heun_chain_f32": (
         C.c_int,
@@ -253,17 +265,18 @@ def call(name: str, *args) -> None:
     while ``cuda:0`` is current would go to a foreign-device stream, and ``hipGetLastError`` /
     the timing events would look at the wrong device."""
     fn = getattr(lib(), name)
-    call_counts[name] += 1
+    booked = BOOKED_AS.get(name, name)
+    call_counts[booked] += 1
     st = args[-1] if args else None
     if isinstance(st, _StreamArg) and st.device_index != torch.cuda.current_device():
         with torch.cuda.device(st.device_index):
-            _call_here(fn, name, args)
+            _call_here(fn, name, booked, args)
         return
-    _call_here(fn, name, args)
+    _call_here(fn, name, booked, args)
 
 
-def _call_here(fn, name: str, args) -> None:
-    pairs = timed_events.get(name)
+def _call_here(fn, name: str, booked: str, args) -> None:
+    pairs = timed_events.get(booked)
     if pairs is None:
         check(fn(*args), name)
         return

@@ -142,6 +142,14 @@ int check_state(const void* x, int64_t n_chains, int32_t dim, const char* who) {
   return 0;
 }
 
+// ebm_langevin_chain_from_f32 on a kernel family that updates in place: the start state goes into the output first
+int copy_state(float* x, const float* src, size_t bytes, hipStream_t st, const char* who) {
+  const hipError_t e = hipMemcpyAsync(x, src, bytes, hipMemcpyDeviceToDevice, st);
+  if (e == hipSuccess) return 0;
+  set_error("%s: copying x_src into x failed: %s", who, hipGetErrorString(e));
+  return (int)e;
+}
+
 }  // namespace
 }  // namespace ebm
 
@@ -195,10 +203,12 @@ int ebm_langevin_step_dev_f32(const float* x, const float* grad, float* out, int
                               rng_state, (hipStream_t)stream);
 }
 
-// The three Langevin chain entries: validate, decode the flag word, build the request -- once, here -- then route it.
+// The four Langevin chain entries: validate, decode the flag word, build the request -- once, here -- then route it.
 // `dev_rng`: ebm_langevin_chain_dev_f32 (RNG coordinates in device memory, MLP energies only; the MLP kernels never contract,
 // so EBM_CHAIN_CONTRACTED is accepted there and ignored).
-static int langevin_chain_impl(const char* who, int heun, bool dev_rng, const ebm_energy_t* energy, float* x, int64_t n_chains,
+// `x_src`: ebm_langevin_chain_from_f32's start state (NULL or x itself: the in-place call).  The element-wise kernels load it in
+// their prologue and store to x; every other family gets it copied into x here, once, and runs in place as before.
+static int langevin_chain_impl(const char* who, int heun, bool dev_rng, const ebm_energy_t* energy, const float* x_src, float* x, int64_t n_chains,
                                int32_t dim, int32_t k_steps, float eta, float sqrt_eta, float noise_coef,
                                const float* coef_table, int32_t clamp_on, float cmin, float cmax, int32_t thin, float* traj,
                                float* diag_partials, const float* noise, uint64_t seed, uint64_t offset,
@@ -216,19 +226,43 @@ static int langevin_chain_impl(const char* who, int heun, bool dev_rng, const eb
     if (energy->kind != EBM_ENERGY_MLP)
       return fail(EBM_EKIND, "%s: device-resident RNG coordinates are taken by the EBM_ENERGY_MLP chain kernels only", who);
   }
-  if (n_chains == 0 || k_steps == 0) return 0;
+  const float* src = x_src ? x_src : x;
+  const size_t state_bytes = (size_t)n_chains * (size_t)dim * sizeof(float);
+  if (src != x) {
+    if (!aligned16(src)) return fail(EBM_EINVAL, "%s: x_src must be 16-byte aligned", who);
+    const uintptr_t s0 = (uintptr_t)src, x0 = (uintptr_t)x;
+    if (s0 < x0 + state_bytes && x0 < s0 + state_bytes)
+      return fail(EBM_EINVAL, "%s: x_src overlaps x without being x (an in-place call passes NULL or x itself)", who);
+  }
+  const hipStream_t st = (hipStream_t)stream;
+  if (n_chains == 0) return 0;
+  if (k_steps == 0) {  // no step: the output is the start state
+    if (src != x) return copy_state(x, src, state_bytes, st, who);
+    return 0;
+  }
   if ((coef_table && !aligned16(coef_table)) || (traj && !aligned16(traj)) || (noise && !aligned16(noise)) ||
       (diag_partials && !aligned16(diag_partials)))
     return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
   if (k_steps / thin == 0) diag_partials = nullptr;
+  const ebm_energy_t& e = *energy;
+  diag::DiagArgs d;
+  const DiagFamily family =
+      diag_partials ? plan_diag(e, heun ? EBM_DIAG_LANGEVIN_HEUN : EBM_DIAG_LANGEVIN, n_chains, dim, noise != nullptr, traj != nullptr, d)
+                    : kDiagNone;
+  // Who reads the start state from `src`: the element-wise launchers (langevin.hip, langevin_diag.hip).  Every other kernel
+  // family updates x in place, so a distinct source is copied into x first and the call goes on as the in-place one.
+  const bool elementwise = e.kind == EBM_ENERGY_DOUBLE_WELL || e.kind == EBM_ENERGY_HARMONIC;
+  const bool launcher_reads_src = diag_partials ? family == kDiagElemFlat : elementwise;
+  const bool no_records = diag_partials && (family == kDiagNone || family == kDiagHmcRows);  // refused below, x left as it is
+  if (src != x && !launcher_reads_src && !no_records) {
+    if (int r = copy_state(x, src, state_bytes, st, who)) return r;
+    src = x;
+  }
   const LangevinChainReq q{*energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef, coef_table,
                            (clamp_on & EBM_CHAIN_CLAMP) != 0, (clamp_on & EBM_CHAIN_CONTRACTED) != 0, cmin, cmax, thin, traj,
-                           noise, seed, offset, diag_partials, heun, rng_state};
-  const ebm_energy_t& e = *energy;
-  const hipStream_t st = (hipStream_t)stream;
+                           noise, seed, offset, diag_partials, heun, rng_state, src};
   if (diag_partials) {
-    diag::DiagArgs d;
-    switch (plan_diag(e, heun ? EBM_DIAG_LANGEVIN_HEUN : EBM_DIAG_LANGEVIN, n_chains, dim, noise != nullptr, traj != nullptr, d)) {
+    switch (family) {
       case kDiagElemFlat: return launch_langevin_chain_elem_diag(q, st);
       case kDiagRows: return launch_langevin_chain_rows(q, st);
       case kDiagMlp: return launch_langevin_chain_mlp(q, st);
@@ -286,15 +320,25 @@ int ebm_langevin_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_chain
                            const float* coef_table, int32_t clamp_on, float cmin, float cmax,
                            int32_t thin, float* traj, float* diag_partials, const float* noise, uint64_t seed,
                            uint64_t offset, void* stream) {
-  return langevin_chain_impl("ebm_langevin_chain_f32", 0, false, energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef,
+  return langevin_chain_impl("ebm_langevin_chain_f32", 0, false, energy, nullptr, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef,
                              coef_table, clamp_on, cmin, cmax, thin, traj, diag_partials, noise, seed, offset, nullptr, stream);
+}
+
+int ebm_langevin_chain_from_f32(const ebm_energy_t* energy, const float* x_src, float* x, int64_t n_chains, int32_t dim,
+                                int32_t k_steps, float eta, float sqrt_eta, float noise_coef,
+                                const float* coef_table, int32_t clamp_on, float cmin, float cmax,
+                                int32_t thin, float* traj, float* diag_partials, const float* noise, uint64_t seed,
+                                uint64_t offset, void* stream) {
+  return langevin_chain_impl("ebm_langevin_chain_from_f32", 0, false, energy, x_src, x, n_chains, dim, k_steps, eta, sqrt_eta,
+                             noise_coef, coef_table, clamp_on, cmin, cmax, thin, traj, diag_partials, noise, seed, offset, nullptr,
+                             stream);
 }
 
 int ebm_langevin_chain_dev_f32(const ebm_energy_t* energy, float* x, int64_t n_chains, int32_t dim, int32_t k_steps,
                                float eta, float sqrt_eta, float noise_coef, const float* coef_table, int32_t clamp_on,
                                float cmin, float cmax, int32_t thin, float* traj, const uint64_t* rng_state,
                                uint64_t step_delta, void* stream) {
-  return langevin_chain_impl("ebm_langevin_chain_dev_f32", 0, true, energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef,
+  return langevin_chain_impl("ebm_langevin_chain_dev_f32", 0, true, energy, nullptr, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef,
                              coef_table, clamp_on, cmin, cmax, thin, traj, nullptr, nullptr, 0, step_delta, rng_state, stream);
 }
 
@@ -303,7 +347,7 @@ int ebm_langevin_heun_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_
                                 const float* coef_table, int32_t clamp_on, float cmin, float cmax,
                                 int32_t thin, float* traj, float* diag_partials, const float* noise, uint64_t seed,
                                 uint64_t offset, void* stream) {
-  return langevin_chain_impl("ebm_langevin_heun_chain_f32", 1, false, energy, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef,
+  return langevin_chain_impl("ebm_langevin_heun_chain_f32", 1, false, energy, nullptr, x, n_chains, dim, k_steps, eta, sqrt_eta, noise_coef,
                              coef_table, clamp_on, cmin, cmax, thin, traj, diag_partials, noise, seed, offset, nullptr, stream);
 }
 

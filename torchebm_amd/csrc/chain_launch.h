@@ -25,6 +25,10 @@ struct LangevinChainReq {
   float* diag_partials;     // null when no step is kept
   int heun;
   const uint64_t* rng_dev;  // ebm_langevin_chain_dev_f32: {seed, step} in device memory (MLP kernels only), else null
+  // The start state [n_chains, dim], read-only; always set, == x for an in-place call.  ebm_langevin_chain_from_f32 passes another
+  // buffer: the element-wise launchers load from it and store to x; for every other family the entry has copied it into x
+  // before the request is routed, and the launcher sees src == x.
+  const float* src;
 
   RngKey key() const { return RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)}; }
   int32_t n_kept() const { return k_steps / thin; }

@@ -130,7 +130,7 @@ __global__ __launch_bounds__(kBlock) void langevin_chain_elem_kernel(ChainArgs a
   const int64_t left = a.n_elem - e0;
   const int nv = left >= 4 ? 4 : (int)left;
 
-  F4 x = load4(a.x, e0, nv, true);
+  F4 x = load4(a.src, e0, nv, true);
 
   // trajectory addressing: traj[c, j, d] with flat e = c*dim + d
   const bool traj_vec = (a.dim & 3) == 0;

@@ -86,12 +86,13 @@ struct ChainArgs {
   uint64_t step0;
   diag::DiagArgs diag;  // per-block diagnostics records at the kept steps (DIAG kernels)
   float fold_eta;       // E = 2^m * eta, 2^m = 4 * s0: the drift coefficient of the folded DoubleWell loop (lean_fold_ok)
+  const float* src;     // the start state, read once in the prologue; == x unless the call came through ebm_langevin_chain_from_f32
 };
 
 // everything but `noise` and `diag`, which the two launchers set apart
 inline ChainArgs elem_chain_args(const LangevinChainReq& q) {
   ChainArgs a{};
-  a.x = q.x; a.n_elem = q.n_chains * (int64_t)q.dim; a.dim = q.dim; a.k_steps = q.k_steps;
+  a.x = q.x; a.src = q.src; a.n_elem = q.n_chains * (int64_t)q.dim; a.dim = q.dim; a.k_steps = q.k_steps;
   a.c = StepCoef{q.eta, q.sqrt_eta, q.noise_coef};
   a.table = reinterpret_cast<const float4*>(q.coef_table);
   a.clamp_on = q.clamp; a.cmin = q.cmin; a.cmax = q.cmax;
@@ -155,7 +156,7 @@ __device__ __forceinline__ void lean_body(const ChainArgs& a) {
   }
   const int64_t left = a.n_elem - e0;
   const int nv = left >= 4 ? 4 : (left > 0 ? (int)left : 0);
-  F4 x = load4(a.x, e0 < a.n_elem ? e0 : 0, nv, true);
+  F4 x = load4(a.src, e0 < a.n_elem ? e0 : 0, nv, true);
   StepCoef c = a.c;
   // lanes past the end of the state (DIAG only) draw from a truncated counter and store nothing
   const PhiloxLane32 rng((uint32_t)g, a.key);

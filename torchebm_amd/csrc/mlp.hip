@@ -48,6 +48,7 @@ int launch_energy_grad_mlp(const ebm_energy_t& e, const float* x, int64_t n_chai
   // an evaluation is a chain of no steps (k_steps == 0)
   LangevinChainReq q{e, const_cast<float*>(x), n_chains, dim};
   q.thin = 1;
+  q.src = q.x;
   return launch_mlp_wide(q, e_out, g_out, st, who);
 }
 

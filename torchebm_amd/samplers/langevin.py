@@ -449,8 +449,10 @@ class LangevinDynamics(BaseSampler):
             self._table_cache = cached
         return cached[1]
 
-    def _launch_chain(self, spec_c, x, n, dim, rows, row0, k, thin, traj, seed, step, stream, table=None, records=None):
-        """One ``ebm_langevin_chain_f32`` launch for steps [row0, row0+k) of ``rows``."""
+    def _launch_chain(self, spec_c, x, n, dim, rows, row0, k, thin, traj, seed, step, stream, table=None, records=None, src=None):
+        """One ``ebm_langevin_chain_f32`` launch for steps [row0, row0+k) of ``rows``.  With ``src`` (the first launch of an
+        out-of-place call, plain Euler-Maruyama only) the chains start from ``src`` and ``x`` is only written:
+        ``ebm_langevin_chain_from_f32``, the same launch and the same states."""
         clamp_on, cmin, cmax = self._clamp_args()
         if len(rows) == 1:  # constant schedule: scalars, no table
             a, sq, coef = rows[0]
@@ -466,8 +468,15 @@ class LangevinDynamics(BaseSampler):
                 clamp_on, cmin, cmax, thin, _lib.ptr(traj), _lib.ptr(coords.tensor), step, stream,
             )
             return
-        entry = "ebm_langevin_heun_chain_f32" if type(self.integrator) is HeunIntegrator else "ebm_langevin_chain_f32"
         flags = clamp_on | (_lib.CHAIN_CONTRACTED if self.fused_arithmetic else 0)  # (ABI 8: a flag word; the bit is a permission)
+        if src is not None:
+            _lib.call(
+                "ebm_langevin_chain_from_f32",
+                spec_c, _lib.ptr(src), _lib.ptr(x), n, dim, k, a, sq, coef, _lib.ptr(tab),
+                flags, cmin, cmax, thin, _lib.ptr(traj), _lib.ptr(records), None, seed, step, stream,
+            )
+            return
+        entry = "ebm_langevin_heun_chain_f32" if type(self.integrator) is HeunIntegrator else "ebm_langevin_chain_f32"
         _lib.call(
             entry,
             spec_c, _lib.ptr(x), n, dim, k, a, sq, coef, _lib.ptr(tab),
@@ -484,8 +493,10 @@ class LangevinDynamics(BaseSampler):
     #: ``config2_fused_arithmetic``).  Calls without such a kernel run the default arithmetic.
     fused_arithmetic: bool = False
 
-    #: Opt-in: let the fused route update the caller's ``x`` in place and return it (no defensive copy of the
-    #: state -- 256 MiB per call at BASELINE config 2).  Off by default: the reference never mutates its input.
+    #: Opt-in: let the fused route update the caller's ``x`` in place and return it.  Off by default: the reference never
+    #: mutates its input.  For the plain Euler-Maruyama call this saves the allocation of the returned state (256 MiB at
+    #: BASELINE config 2), not a copy: the default call reads the caller's tensor and writes a fresh one in the same launch
+    #: (``ebm_langevin_chain_from_f32``).  Heun calls and calls captured by ``utils.GraphedTrainingStep`` still copy first.
     donate_input: bool = False
 
     #: upper bound on the bytes of per-block diagnostics records held at once; longer runs are cut into several
@@ -496,12 +507,20 @@ class LangevinDynamics(BaseSampler):
         n, dim = x.shape
         n_kept = n_steps // thin
         state = _lib.dense_f32(x)
-        if state.data_ptr() == x.data_ptr() and not self.donate_input:
-            state = state.clone()  # the kernel updates in place; never touch the caller's tensor unless it was donated
-        traj, diag = self._new_outputs(x, n_kept, want_traj, want_diag)
-        _, rows = self._coef_rows(n_steps)
         coords = getattr(self, "_graph_coords", None)
         heun = type(self.integrator) is HeunIntegrator
+        src = None  # the caller's tensor as the read-only start state of the call's first launch
+        if state.data_ptr() == x.data_ptr() and not self.donate_input:
+            # Never touch the caller's tensor unless it was donated.  The plain Euler-Maruyama call starts from it out of place
+            # (ebm_langevin_chain_from_f32) and writes a fresh tensor, which only a launch fills: a call without one keeps the
+            # copy.  So do Heun (ebm_langevin_heun_chain_f32 has no out-of-place entry) and a call under capture in a
+            # training-step graph (ebm_langevin_chain_dev_f32 has none either): those kernels update a copy in place.
+            if not heun and coords is None and n_steps > 0 and n > 0:
+                src, state = state, torch.empty_like(state, memory_format=torch.contiguous_format)
+            else:
+                state = state.clone()
+        traj, diag = self._new_outputs(x, n_kept, want_traj, want_diag)
+        _, rows = self._coef_rows(n_steps)
         if coords is not None:
             # utils.graphed_step is capturing this call: coordinates come from device memory (ebm_langevin_chain_dev_f32)
             if want_diag or heun or spec.kind != _lib.ENERGY_MLP or len(rows) != 1:
@@ -521,16 +540,16 @@ class LangevinDynamics(BaseSampler):
                 layout = _lib.diag_layout(spec_c, _lib.DIAG_LANGEVIN_HEUN if heun else _lib.DIAG_LANGEVIN, n, dim, False, want_traj)
             if not want_diag or n_kept == 0:
                 # one launch for the whole call; thinned rows are stored by the kernel
-                self._launch_chain(spec_c, state, n, dim, rows, 0, n_steps, thin, traj, seed, step0, stream)
+                self._launch_chain(spec_c, state, n, dim, rows, 0, n_steps, thin, traj, seed, step0, stream, src=src)
             elif layout is not None:
-                self._fused_with_records(spec_c, state, n, dim, rows, n_steps, thin, traj, diag, layout, seed, step0, stream)
+                self._fused_with_records(spec_c, state, n, dim, rows, n_steps, thin, traj, diag, layout, seed, step0, stream, src=src)
             else:
-                self._fused_with_state_passes(spec_c, state, n, dim, rows, n_steps, thin, traj, diag, seed, step0, stream)
+                self._fused_with_state_passes(spec_c, state, n, dim, rows, n_steps, thin, traj, diag, seed, step0, stream, src=src)
         self.advance_schedulers(n_steps)
         out = traj if want_traj else state
         return (out, diag) if want_diag else out
 
-    def _fused_with_records(self, spec_c, state, n, dim, rows, n_steps, thin, traj, diag, layout, seed, step0, stream):
+    def _fused_with_records(self, spec_c, state, n, dim, rows, n_steps, thin, traj, diag, layout, seed, step0, stream, src=None):
         """Diagnostics from inside the chain launch (include/ebm_hip.h: ``diag_partials``): every workgroup stores
         one record of its chains' partial sums per kept step, ``ebm_diag_finish_f32`` merges them.  One chain
         launch + one merge launch per call (several only when the records of all kept steps would not fit
@@ -558,7 +577,8 @@ class LangevinDynamics(BaseSampler):
             whole = traj is not None and kk == n_kept
             piece = traj if (traj is None or whole) else torch.empty(n, kk, dim, dtype=torch.float32, device=state.device)
             self._launch_chain(spec_c, state, n, dim, rows, done_steps, steps, thin, piece, seed, step0 + done_steps, stream,
-                               records=records)
+                               records=records, src=src)
+            src = None  # the first launch only: every later one continues in place on `state`
             if traj is not None and not whole:
                 traj[:, done_keep : done_keep + kk] = piece
             sl = slice(done_keep, done_keep + kk)
@@ -583,7 +603,7 @@ class LangevinDynamics(BaseSampler):
             done_steps += steps
         _record_scratch_done(self)
 
-    def _fused_with_state_passes(self, spec_c, state, n, dim, rows, n_steps, thin, traj, diag, seed, step0, stream):
+    def _fused_with_state_passes(self, spec_c, state, n, dim, rows, n_steps, thin, traj, diag, seed, step0, stream, src=None):
         """Diagnostics for the configurations without in-kernel records (the matrix-layout kernels of the MLP
         energy, rows that neither divide nor are divided by the flat kernel's 1024-element blocks): one launch per
         ``thin`` steps, then the column-statistics and energy kernels on the state."""
@@ -596,7 +616,8 @@ class LangevinDynamics(BaseSampler):
         wide_gaussian = type(self.model) is GaussianModel and dim > GaussianModel.CLOSED_FORM_GRADIENT_ABOVE
         done = 0
         for keep in range(n_kept):
-            self._launch_chain(spec_c, state, n, dim, rows, done, thin, thin, None, seed, step0 + done, stream)
+            self._launch_chain(spec_c, state, n, dim, rows, done, thin, thin, None, seed, step0 + done, stream, src=src)
+            src = None  # the first launch only: every later one continues in place on `state`
             done += thin
             if traj is not None:
                 traj[:, keep] = state
