@@ -331,6 +331,57 @@ EBM_API int ebm_tempering_chain_f32(const ebm_energy_t* energy, float* x, int64_
                                     int32_t swap_every, int32_t thin, float* traj, uint32_t* swap_counts, const float* noise,
                                     const float* u, uint64_t seed, uint64_t step0, void* stream);
 
+/*
+ * Replica-exchange HMC: the ladders of ebm_tempering_chain_f32 with a Metropolis-corrected HMC transition in every slot instead
+ * of an Euler-Maruyama step -- n_mh transitions of every slot and the swap events between them in ONE launch (an addition to
+ * ABI 9: nothing else moved).  No slot carries a discretisation bias.
+ *
+ * State: x is the SLOT MATRIX [n_ladders * n_replicas, dim], updated in place; row c * R + r is slot r of ladder c, slot 0 the
+ * target.  Slot r samples exp(-beta_r E) with the mass M = beta_r I; in the velocity variable w = p / beta_r that is the ordinary
+ * leapfrog on E itself at the kinetic temperature T_r.  The host sends three device arrays of length R:
+ * sqrt_temp[r] = (float)sqrt(T_r) and beta[r] = (float)(1 / T_r), formed in double and rounded once, and eps[r], the slot's step
+ * size.
+ *
+ * Transition t (0 .. n_mh - 1), every slot:
+ *   1. w = z * sqrt_temp[r]; z is the normal field at Philox step step0 + 3 t, element (c * R + r) * dim + col
+ *   2. H0 = clamp(E(x), +-1e10) + clamp(0.5 sum w^2, 0, 1e10)
+ *   3. n_leapfrog safe-mode leapfrog steps on E with the step size eps[r] (the force clamp +-1e6 and the NaN scrubs of
+ *      ebm_hmc_chain_f32; the same carried energy and force, merged kicks and literal fallback)
+ *   4. H1 the same way from the proposal
+ *   5. d = clamp(beta[r] * (H0 - H1), +-50), a = min(1, exp d)
+ *   6. the proposal is accepted iff u < a; u is the uniform field at step step0 + 3 t + 1, element c * R + r.  A NaN rejects.
+ *
+ * Swap event m = (t + 1) / swap_every - 1 follows transition t when (t + 1) % swap_every == 0; the pairing by the parity of m
+ * and the rule are those of ebm_tempering_chain_f32: delta = (beta[r] - beta[r + 1]) * (E_r - E_{r+1}) on the raw fp32 energies
+ * of the states the slots now hold (an accepted proposal's E1, else E0: the energies the transitions carry -- an event evaluates
+ * nothing), and the pair swaps iff delta == delta and u < exp(min(delta, 0)), u the uniform field at step step0 + 3 t + 2,
+ * element c * R + r: the lower slot's row.  Nothing a state carries (x, E(x), the force) depends on the temperature, so a swap
+ * exchanges the labels: slot index, eps, sqrt_temp, beta.  A call consumes the Philox steps step0 .. step0 + 3 n_mh - 1.
+ *
+ * After transition t and its event, slot 0's state goes to traj[c, (t + 1) / thin - 1] whenever (t + 1) % thin == 0
+ * (traj: [n_ladders, n_mh / thin, dim], or NULL).
+ * accept_mask: NULL, or uint8[n_mh, n_ladders * R] indexed by slot row (1 = the slot's proposal was accepted).
+ * accept_counts: NULL, or device uint32[R] the call ADDS to: accepted proposals per slot over the call (n_mh * n_ladders were
+ * proposed in each).  swap_counts: NULL, or device uint32[2 * (R - 1)] the call ADDS to, as in ebm_tempering_chain_f32.
+ * p_noise / u_accept / u_swap: all three NULL (native draws) or all three given: p_noise[n_mh, n_ladders * R, dim],
+ * u_accept[n_mh, n_ladders * R], u_swap[n_events, n_ladders * R] (n_events = n_mh / swap_every; lower-slot entries are read).
+ *
+ * Consequences: with beta = sqrt_temp = 1 in every slot and no event, the rows are ebm_hmc_chain_f32 chains (identity mass) on
+ * the lane-group kernel of the same geometry, bit for bit.  On a quadratic energy one step size gives every slot the same
+ * acceptance (the trajectory scales with sqrt(T) and beta undoes it in d); eps[R] exists for quartic walls and the like, where
+ * a hot slot needs a shorter step.
+ *
+ * Lane-group kernels (one lane group per walker, one vector per lane): identity mass; every analytic energy except EBM_ENERGY_MLP
+ * (EBM_EKIND); dim <= 256 (EBM_EDIM); 2 <= n_replicas <= 64 and n_replicas * G <= 256 with G = the lanes per row, the power of
+ * two >= ceil(dim / 4) (EBM_EDIM otherwise).  swap_every >= 1, thin >= 1, n_leapfrog >= 1.  Constant step sizes only; no
+ * diagnostics records.
+ */
+EBM_API int ebm_tempering_hmc_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_ladders, int32_t n_replicas, int32_t dim,
+                                        int32_t n_mh, int32_t n_leapfrog, const float* eps, const float* sqrt_temp,
+                                        const float* beta, int32_t swap_every, int32_t thin, float* traj, uint8_t* accept_mask,
+                                        uint32_t* accept_counts, uint32_t* swap_counts, const float* p_noise,
+                                        const float* u_accept, const float* u_swap, uint64_t seed, uint64_t step0, void* stream);
+
 /* The accept step with the RNG coordinates in DEVICE memory (rng_state = {seed, step}; the uniforms
  * are drawn at step rng_state[1] + step_delta): the graph-capturable form, see
  * ebm_langevin_step_dev_f32.  No injected-uniform form. */

@@ -426,6 +426,32 @@ int ebm_tempering_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_ladd
   return tempering_chain_launch(q, (hipStream_t)stream);
 }
 
+int ebm_tempering_hmc_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_ladders, int32_t n_replicas, int32_t dim,
+                                int32_t n_mh, int32_t n_leapfrog, const float* eps, const float* sqrt_temp, const float* beta,
+                                int32_t swap_every, int32_t thin, float* traj, uint8_t* accept_mask, uint32_t* accept_counts,
+                                uint32_t* swap_counts, const float* p_noise, const float* u_accept, const float* u_swap,
+                                uint64_t seed, uint64_t step0, void* stream) {
+  const char* who = "ebm_tempering_hmc_chain_f32";
+  if (energy && energy->kind == EBM_ENERGY_MLP)
+    return fail(EBM_EKIND, "%s: the MLP energy has no replica-exchange kernel (the sampler's eager route takes it)", who);
+  if (int r = check_energy(energy, dim, who)) return r;
+  if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
+  if (n_replicas < 2 || n_replicas > 64) return fail(EBM_EINVAL, "%s: n_replicas=%d (a ladder has 2 .. 64 slots)", who, n_replicas);
+  if (n_ladders < 0 || dim < 1) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d, %d]", who, (long long)n_ladders, n_replicas, dim);
+  if (!aligned16(x)) return fail(EBM_EINVAL, "%s: state pointer must be 16-byte aligned", who);
+  if (n_mh < 0 || n_leapfrog < 1 || swap_every < 1 || thin < 1)
+    return fail(EBM_EINVAL, "%s: n_mh=%d n_leapfrog=%d swap_every=%d thin=%d", who, n_mh, n_leapfrog, swap_every, thin);
+  if (int r = tempering_hmc_check_geometry(n_replicas, dim)) return r;
+  if (!eps || !sqrt_temp || !beta) return fail(EBM_EINVAL, "%s: eps / sqrt_temp / beta is NULL", who);
+  if ((p_noise == nullptr) != (u_accept == nullptr) || (p_noise == nullptr) != (u_swap == nullptr))
+    return fail(EBM_EINVAL, "%s: p_noise, u_accept and u_swap must be given together", who);
+  if (n_ladders == 0 || n_mh == 0) return 0;
+  if ((traj && !aligned16(traj)) || (p_noise && !aligned16(p_noise))) return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  const TemperingHmcChainReq q{*energy, x, n_ladders, n_replicas, dim, n_mh, n_leapfrog, eps, sqrt_temp, beta, swap_every, thin,
+                               traj, accept_mask, accept_counts, swap_counts, p_noise, u_accept, u_swap, seed, step0};
+  return tempering_hmc_chain_launch(q, (hipStream_t)stream);
+}
+
 int ebm_leapfrog_kick_drift_f32(const float* x, const float* p, const float* force, float* x_new,
                                 float* p_half, int64_t n_chains, int32_t dim, float eps,
                                 int32_t mass_kind, double mass_scalar, const float* mass_diag,

@@ -76,6 +76,28 @@ struct TemperingChainReq {
   int32_t n_kept() const { return k_steps / thin; }
 };
 
+struct TemperingHmcChainReq {
+  const ebm_energy_t& e;
+  float* x;                // the slot matrix [n_ladders * n_replicas, dim]
+  int64_t n_ladders;
+  int32_t n_replicas, dim, n_mh, n_leapfrog;
+  const float* eps;        // device [n_replicas]: the slots' step sizes
+  const float* sqrt_temp;  // device [n_replicas]
+  const float* beta;       // device [n_replicas]
+  int32_t swap_every, thin;
+  float* traj;
+  uint8_t* accept_mask;
+  uint32_t* accept_counts;
+  uint32_t* swap_counts;
+  const float* p_noise;
+  const float* u_accept;
+  const float* u_swap;
+  uint64_t seed, offset;
+
+  RngKey key() const { return RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)}; }
+  int32_t n_kept() const { return n_mh / thin; }
+};
+
 // The fields the row-major Langevin argument structs share (GaussArgs, BigArgs, RowChainArgs, WideArgs).
 template <class Args>
 inline void fill_langevin(Args& a, const LangevinChainReq& q) {
@@ -172,5 +194,11 @@ bool matrix_hmc_diag_plan(const ebm_energy_t&, int64_t n_chains, int32_t dim, di
 // ---------------------------------------------------------------------------------
 int tempering_chain_launch(const TemperingChainReq&, hipStream_t);
 int tempering_check_geometry(int32_t n_replicas, int32_t dim);  // 0, or the refusal (dim > 1024, ladder wider than a workgroup)
+
+// ---------------------------------------------------------------------------------
+// Replica-exchange HMC (tempering_hmc.hip: the same ladders, a Metropolis-corrected HMC transition in every slot)
+// ---------------------------------------------------------------------------------
+int tempering_hmc_chain_launch(const TemperingHmcChainReq&, hipStream_t);
+int tempering_hmc_check_geometry(int32_t n_replicas, int32_t dim);  // 0, or the refusal (dim > 256, ladder wider than a workgroup)
 
 }  // namespace ebm

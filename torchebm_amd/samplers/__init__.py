@@ -3,7 +3,7 @@
 from .descent import GradientDescentSampler, NesterovSampler
 from .hamiltonian import HamiltonianMonteCarlo
 from .langevin import LangevinDynamics
-from .tempering import ReplicaExchangeLangevin
+from .tempering import ReplicaExchangeHMC, ReplicaExchangeLangevin
 
 __all__ = ["LangevinDynamics", "HamiltonianMonteCarlo", "GradientDescentSampler", "NesterovSampler",
-           "ReplicaExchangeLangevin"]
+           "ReplicaExchangeLangevin", "ReplicaExchangeHMC"]
