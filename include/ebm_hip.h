@@ -382,6 +382,45 @@ EBM_API int ebm_tempering_hmc_chain_f32(const ebm_energy_t* energy, float* x, in
                                         uint32_t* accept_counts, uint32_t* swap_counts, const float* p_noise,
                                         const float* u_accept, const float* u_swap, uint64_t seed, uint64_t step0, void* stream);
 
+/*
+ * Annealed importance sampling (Neal 2001): every chain walks ONE state from the base N(0, sigma0^2 I) to the target through
+ * n_temps tempered laws and accumulates the importance weight whose mean estimates Z / Z_0 -- the whole walk in ONE launch (an
+ * addition to ABI 9: nothing else moved).  The third member of the tempered family: the replica-exchange entries run R
+ * temperatures side by side, this one runs T = n_temps of them in time.
+ *
+ * Base and path: E_0(x) = 0.5 * inv_var0 * sum x^2 (log Z_0 = dim / 2 * log(2 pi sigma0^2)), U_b(x) = (1 - b) E_0(x) + b E(x).
+ * beta: device float[T + 1], beta[0] = 0, beta[T] = 1, non-decreasing; eps: device float[T], the step size of transition t at
+ * eps[t - 1].  The host forms the schedule in double and rounds once; sigma0 = (float)sigma_0, inv_var0 = (float)(1 / sigma_0^2).
+ *
+ * Start: x = sigma0 * z, z the normal field at Philox step step0, element chain * dim + col -- or the injected x0[n, dim];
+ * logw = 0.
+ * Step t = 1 .. T, every chain:
+ *   1. logw += (beta[t] - beta[t - 1]) * (E_0(x) - E(x)): difference and product in fp32, on the energies of the state the
+ *      chain holds (carried from the previous transition: the update evaluates nothing); the running sum is a compensated
+ *      (Kahan) fp32 pair per chain.
+ *   2. one Metropolis-corrected HMC transition that leaves exp(-U_{beta[t]}) invariant: identity mass, n_leapfrog safe-mode
+ *      leapfrog steps of size eps[t - 1] with the force clamp(-((1 - b) inv_var0 x + b dE/dx), +-1e6) (the NaN scrubs, merged
+ *      kicks and literal fallback of ebm_hmc_chain_f32), H = clamp(U, +-1e10) + clamp(0.5 sum p^2, 0, 1e10),
+ *      d = clamp(H0 - H1, +-50), accepted iff u < min(1, exp d); a NaN rejects.  The momentum is the normal field at step
+ *      step0 + 2 t - 1, element chain * dim + col; u the uniform field at step step0 + 2 t, element chain.
+ * A call consumes the Philox steps step0 .. step0 + 2 T.
+ *
+ * Out: logw[n]; x[n, dim], the final states (written once, never read: approximately target samples that carry the weights).
+ * accept_mask: NULL, or uint8[T, n] (row t - 1: transition t).  accept_counts: NULL, or device uint32[T] the call ADDS to:
+ * accepted proposals of each temperature (n were proposed at each) -- what eps[t] is tuned with.
+ * x0 / p_noise / u_accept: all three NULL (native draws) or all three given: x0[n, dim], p_noise[T, n, dim], u_accept[T, n].
+ *
+ * Consequence: the mix is formed as (1 - b) * a + b * c, never divided by b, so at b = 1 the transition is ebm_hmc_chain_f32's
+ * on the lane-group kernel of the same geometry, bit for bit (finite states).
+ *
+ * Lane-group kernels (one lane group per chain, one vector per lane, no exchange between chains): every analytic energy except
+ * EBM_ENERGY_MLP (EBM_EKIND); dim <= 256 (EBM_EDIM, in front of any device access); n_temps >= 1, n_leapfrog >= 1.
+ */
+EBM_API int ebm_ais_chain_f32(const ebm_energy_t* energy, float* x, float* logw, int64_t n_chains, int32_t dim, int32_t n_temps,
+                              int32_t n_leapfrog, const float* beta, const float* eps, float sigma0, float inv_var0,
+                              uint8_t* accept_mask, uint32_t* accept_counts, const float* x0, const float* p_noise,
+                              const float* u_accept, uint64_t seed, uint64_t step0, void* stream);
+
 /* The accept step with the RNG coordinates in DEVICE memory (rng_state = {seed, step}; the uniforms
  * are drawn at step rng_state[1] + step_delta): the graph-capturable form, see
  * ebm_langevin_step_dev_f32.  No injected-uniform form. */

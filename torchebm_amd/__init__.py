@@ -19,4 +19,10 @@ from .core import (  # noqa: F401
 )
 from .integrators import EulerMaruyamaIntegrator, LeapfrogIntegrator  # noqa: F401
 from .losses import ContrastiveDivergence, EnergyMatchingContrastive  # noqa: F401
-from .samplers import HamiltonianMonteCarlo, LangevinDynamics, ReplicaExchangeHMC, ReplicaExchangeLangevin  # noqa: F401
+from .samplers import (  # noqa: F401
+    AnnealedImportanceSampling,
+    HamiltonianMonteCarlo,
+    LangevinDynamics,
+    ReplicaExchangeHMC,
+    ReplicaExchangeLangevin,
+)

@@ -98,6 +98,25 @@ struct TemperingHmcChainReq {
   int32_t n_kept() const { return n_mh / thin; }
 };
 
+struct AisChainReq {
+  const ebm_energy_t& e;
+  float* x;                // [n_chains, dim]: the final states, written once
+  float* logw;             // [n_chains]
+  int64_t n_chains;
+  int32_t dim, n_temps, n_leapfrog;
+  const float* beta;       // device [n_temps + 1]
+  const float* eps;        // device [n_temps]: the step size of every transition
+  float sigma0, inv_var0;  // the base N(0, sigma0^2 I)
+  uint8_t* accept_mask;
+  uint32_t* accept_counts;
+  const float* x0;
+  const float* p_noise;
+  const float* u_accept;
+  uint64_t seed, offset;
+
+  RngKey key() const { return RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)}; }
+};
+
 // The fields the row-major Langevin argument structs share (GaussArgs, BigArgs, RowChainArgs, WideArgs).
 template <class Args>
 inline void fill_langevin(Args& a, const LangevinChainReq& q) {
@@ -200,5 +219,11 @@ int tempering_check_geometry(int32_t n_replicas, int32_t dim);  // 0, or the ref
 // ---------------------------------------------------------------------------------
 int tempering_hmc_chain_launch(const TemperingHmcChainReq&, hipStream_t);
 int tempering_hmc_check_geometry(int32_t n_replicas, int32_t dim);  // 0, or the refusal (dim > 256, ladder wider than a workgroup)
+
+// ---------------------------------------------------------------------------------
+// Annealed importance sampling (ais.hip: one walker per chain through the temperatures in time, the weight from carried energies)
+// ---------------------------------------------------------------------------------
+int ais_chain_launch(const AisChainReq&, hipStream_t);
+int ais_check_geometry(int32_t dim);  // 0, or the refusal (dim > 256)
 
 }  // namespace ebm

@@ -1,9 +1,10 @@
 """Samplers (reference package: torchebm/samplers)."""
 
+from .ais import AISResult, AnnealedImportanceSampling
 from .descent import GradientDescentSampler, NesterovSampler
 from .hamiltonian import HamiltonianMonteCarlo
 from .langevin import LangevinDynamics
 from .tempering import ReplicaExchangeHMC, ReplicaExchangeLangevin
 
 __all__ = ["LangevinDynamics", "HamiltonianMonteCarlo", "GradientDescentSampler", "NesterovSampler",
-           "ReplicaExchangeLangevin", "ReplicaExchangeHMC"]
+           "ReplicaExchangeLangevin", "ReplicaExchangeHMC", "AnnealedImportanceSampling", "AISResult"]
