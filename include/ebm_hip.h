@@ -421,6 +421,43 @@ EBM_API int ebm_ais_chain_f32(const ebm_energy_t* energy, float* x, float* logw,
                               uint8_t* accept_mask, uint32_t* accept_counts, const float* x0, const float* p_noise,
                               const float* u_accept, uint64_t seed, uint64_t step0, void* stream);
 
+/*
+ * Annealed importance sampling on EBM_ENERGY_MLP -- the energy the package trains -- in ONE launch (an addition to ABI 9:
+ * nothing else moved; ebm_ais_chain_f32 keeps refusing the MLP).  Parameters, base, path, draws and outputs are exactly those of
+ * ebm_ais_chain_f32 above; what differs is where the energies of step 1 come from:
+ *
+ * Start: x = sigma0 * z, z the normal field at Philox step step0, element chain * dim + col -- or the injected x0[n, dim];
+ * logw = 0.
+ * Step t = 1 .. T, every chain, with db = beta[t] - beta[t - 1], b = beta[t], b0 = 1 - b, c0 = b0 * inv_var0 formed in fp32:
+ *   1. ONE evaluation at the held state gives E(x) and dE/dx; E_0(x) = 0.5 * inv_var0 * sum x^2.
+ *      logw += db * (E_0 - E), the running sum a compensated (Kahan) fp32 pair per chain; an infinite sum stays what a plain
+ *      sum gives.
+ *   2. one Metropolis-corrected HMC transition that leaves exp(-U_b) invariant: identity mass, momentum the normal field at
+ *      step step0 + 2 t - 1, H0 = clamp(b0 * E_0 + b * E, +-1e10) + clamp(0.5 sum p^2, 0, 1e10), the first force
+ *      clamp(-(c0 * x + b * dE/dx), +-1e6) from the evaluation of 1., n_leapfrog safe-mode leapfrog steps of size eps[t - 1]
+ *      (one evaluation each: the same mix of its gradient is the next force; NaN scrubs, merged kicks and literal fallback of
+ *      ebm_hmc_chain_f32), H1 from U = b0 * E_0(x') + b * E(x'), d = clamp(H0 - H1, +-50), accepted iff u < min(1, exp d), u the
+ *      uniform field at step step0 + 2 t, element chain; a NaN rejects.
+ * A transition costs n_leapfrog + 1 evaluations, as ebm_hmc_chain_f32's on this energy.  A call consumes the Philox steps
+ * step0 .. step0 + 2 T.
+ *
+ * The evaluation is the matrix-core one of ebm_hmc_chain_f32 / ebm_energy_grad_f32 (three-way split bf16 operands or exact-f32
+ * MFMA, fp32 accumulation): fp32 accuracy, not autograd's rounding.  One wave walks 32 chains.
+ * x is output only: the kernel keeps the held state there between transitions and never reads a word it has not written.
+ *
+ * Consequence: at b = 1 the mix is 0 * a + 1 * c = c, and the transition is ebm_hmc_chain_f32's on this energy with the same
+ * injected draws (identity mass), bit for bit (finite states).
+ *
+ * Refusals, all in front of any device access: a NULL energy, x, logw, beta or eps, n_temps < 1, n_leapfrog < 1, or x0 /
+ * p_noise / u_accept not given together (EBM_EINVAL); a kind other than EBM_ENERGY_MLP (EBM_EKIND); a hidden width
+ * (energy->n_comp) other than 64 / 128 or dim outside 1 .. 128 (EBM_EDIM).  Identity mass only; no trajectory, no thinning, no
+ * diagnostics records; no H = 256, no pre-split W1 image (energy->aux is ignored).
+ */
+EBM_API int ebm_ais_mlp_chain_f32(const ebm_energy_t* energy, float* x, float* logw, int64_t n_chains, int32_t dim, int32_t n_temps,
+                                  int32_t n_leapfrog, const float* beta, const float* eps, float sigma0, float inv_var0,
+                                  uint8_t* accept_mask, uint32_t* accept_counts, const float* x0, const float* p_noise,
+                                  const float* u_accept, uint64_t seed, uint64_t step0, void* stream);
+
 /* The accept step with the RNG coordinates in DEVICE memory (rng_state = {seed, step}; the uniforms
  * are drawn at step rng_state[1] + step_delta): the graph-capturable form, see
  * ebm_langevin_step_dev_f32.  No injected-uniform form. */

@@ -474,6 +474,30 @@ int ebm_ais_chain_f32(const ebm_energy_t* energy, float* x, float* logw, int64_t
   return ais_chain_launch(q, (hipStream_t)stream);
 }
 
+int ebm_ais_mlp_chain_f32(const ebm_energy_t* energy, float* x, float* logw, int64_t n_chains, int32_t dim, int32_t n_temps,
+                          int32_t n_leapfrog, const float* beta, const float* eps, float sigma0, float inv_var0, uint8_t* accept_mask,
+                          uint32_t* accept_counts, const float* x0, const float* p_noise, const float* u_accept, uint64_t seed,
+                          uint64_t step0, void* stream) {
+  const char* who = "ebm_ais_mlp_chain_f32";
+  if (int r = check_energy(energy, dim, who)) return r;
+  if (energy->kind != EBM_ENERGY_MLP)
+    return fail(EBM_EKIND, "%s: this entry walks the MLP energy only (ebm_ais_chain_f32 takes the analytic kinds)", who);
+  if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
+  if (!logw) return fail(EBM_EINVAL, "%s: logw is NULL", who);
+  if (n_chains < 0) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d]", who, (long long)n_chains, dim);
+  if (n_temps < 1 || n_leapfrog < 1) return fail(EBM_EINVAL, "%s: n_temps=%d n_leapfrog=%d", who, n_temps, n_leapfrog);
+  if (!beta || !eps) return fail(EBM_EINVAL, "%s: beta / eps is NULL", who);
+  if ((x0 == nullptr) != (p_noise == nullptr) || (x0 == nullptr) != (u_accept == nullptr))
+    return fail(EBM_EINVAL, "%s: x0, p_noise and u_accept must be given together", who);
+  if (int r = ais_mlp_check_shape(energy->n_comp, dim)) return r;
+  if (!aligned16(x)) return fail(EBM_EINVAL, "%s: state pointer must be 16-byte aligned", who);
+  if (n_chains == 0) return 0;
+  if ((x0 && !aligned16(x0)) || (p_noise && !aligned16(p_noise))) return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  const AisChainReq q{*energy, x, logw, n_chains, dim, n_temps, n_leapfrog, beta, eps, sigma0, inv_var0, accept_mask, accept_counts,
+                      x0, p_noise, u_accept, seed, step0};
+  return ais_mlp_chain_launch(q, (hipStream_t)stream);
+}
+
 int ebm_leapfrog_kick_drift_f32(const float* x, const float* p, const float* force, float* x_new,
                                 float* p_half, int64_t n_chains, int32_t dim, float eps,
                                 int32_t mass_kind, double mass_scalar, const float* mass_diag,

@@ -225,5 +225,8 @@ int tempering_hmc_check_geometry(int32_t n_replicas, int32_t dim);  // 0, or the
 // ---------------------------------------------------------------------------------
 int ais_chain_launch(const AisChainReq&, hipStream_t);
 int ais_check_geometry(int32_t dim);  // 0, or the refusal (dim > 256)
+// ... on the MLP energy (mlp_wide_ais.hip: the same request; 32 chains per wave around the matrix-core evaluation, n_leapfrog + 1 of them per transition)
+int ais_mlp_chain_launch(const AisChainReq&, hipStream_t);
+int ais_mlp_check_shape(int32_t hidden, int32_t dim);  // 0, or the refusal (hidden width not 64 / 128, dim outside 1 .. 128)
 
 }  // namespace ebm

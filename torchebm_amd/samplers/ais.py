@@ -13,6 +13,10 @@ Two execution routes, chosen once per ``run()`` call (``_route``):
            weight updates and transitions, Philox draws, per-temperature accept counters -- is ONE launch of
            ``ebm_ais_chain_f32`` (docs/design/ais.md).  The third member of the tempered family: the replica-exchange
            samplers run the temperatures side by side, this one runs them in time.
+``fused_mlp``  opt-in (``sampler.fused_mlp = True``): CUDA fp32, an ``MLPEnergy`` of hidden width 64 / 128 and
+           ``dim == in_dim <= 128``: the whole estimate is ONE launch of ``ebm_ais_mlp_chain_f32`` (docs/design/ais_mlp.md), the
+           evaluation on the matrix cores inside the transition.  Its energies are the kernel's (fp32-accurate, not autograd's
+           rounding), so the default stays ``eager`` for the MLP and an estimate made without the opt-in is bit for bit what it was.
 ``eager``  everything else (CPU, ``MLPEnergy`` or a hand-written energy, wider states, other dtypes): the same algorithm in
            torch ops, drawing ``randn(n, dim)`` for the start and then ``randn(n, dim)`` and ``rand(n)`` per step.
 
@@ -99,8 +103,13 @@ class AnnealedImportanceSampling(TorchEBMModule):
 
     Routes (``_route``): ``fused`` -- CUDA fp32, an analytic energy (not the MLP), ``dim <= 256``: ONE launch of
     ``ebm_ais_chain_f32`` per ``run()``, never a fallback; ``eager`` -- everything else, the same algorithm in torch ops,
-    drawing ``randn(n, dim)`` for the start, then ``randn(n, dim)`` and ``rand(n)`` per step.
+    drawing ``randn(n, dim)`` for the start, then ``randn(n, dim)`` and ``rand(n)`` per step; ``fused_mlp`` -- the opt-in below.
     """
+
+    #: opt-in: an ``MLPEnergy`` (hidden 64 / 128, ``dim == in_dim <= 128``, CUDA fp32, no autocast) runs as ONE launch of
+    #: ``ebm_ais_mlp_chain_f32`` instead of the eager route.  Off by default: the fused evaluation is three-way-split bf16
+    #: arithmetic at fp32 accuracy, not autograd's rounding, and the draws are the Philox field's, not torch's.
+    fused_mlp = False
 
     def __init__(
         self,
@@ -163,7 +172,12 @@ class AnnealedImportanceSampling(TorchEBMModule):
         if self.use_mixed_precision and self.autocast_available:
             return "eager", None
         spec = fused_spec_for(self.model, torch.empty(0, dim, dtype=self.dtype, device=self.device), None)
-        if spec is None or spec.kind == _lib.ENERGY_MLP:
+        if spec is None:
+            return "eager", None
+        if spec.kind == _lib.ENERGY_MLP:
+            if (self.fused_mlp and spec.hmc and spec.n_comp in (64, 128) and dim == getattr(self.model, "in_dim", None)
+                    and dim <= 128):
+                return "fused_mlp", spec
             return "eager", None
         return "fused", spec
 
@@ -179,6 +193,8 @@ class AnnealedImportanceSampling(TorchEBMModule):
         route, spec = self._route(dim)
         if route == "fused":
             logw, x, accepted = self._run_fused(spec, n, dim, generator)
+        elif route == "fused_mlp":
+            logw, x, accepted = self._run_fused(spec, n, dim, generator, entry="ebm_ais_mlp_chain_f32")
         else:
             logw, x, accepted = self._run_eager(n, dim, generator)
         log_z, stderr, ess, bad = ais_estimate(logw, self.log_z0(dim))
@@ -238,14 +254,14 @@ class AnnealedImportanceSampling(TorchEBMModule):
         return logw, x, accepted.to(dev)
 
     # ---------------------------------------------------------------------------------
-    # route: one launch of ebm_ais_chain_f32
+    # routes: one launch of ebm_ais_chain_f32, or (fused_mlp) of ebm_ais_mlp_chain_f32 -- the same parameter list
     # ---------------------------------------------------------------------------------
     def _tables_on(self, device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
         if self._tables is None or self._tables[0] != device:
             self._tables = (device, self.betas.to(device), self.step_sizes.to(device))
         return self._tables[1], self._tables[2]
 
-    def _run_fused(self, spec: FusedSpec, n: int, dim: int, generator):
+    def _run_fused(self, spec: FusedSpec, n: int, dim: int, generator, entry: str = "ebm_ais_chain_f32"):
         dev, T = self.device, self.n_temperatures
         sigma0, inv_var0 = self.base_coefficients()
         betas, eps = self._tables_on(dev)
@@ -254,7 +270,7 @@ class AnnealedImportanceSampling(TorchEBMModule):
         counts = torch.zeros(T, dtype=torch.int32, device=dev)    # (uint32 counters in an int32 tensor)
         seed, step0 = _rng.reserve(generator, dev, 2 * T + 1)
         _lib.call(
-            "ebm_ais_chain_f32",
+            entry,
             spec.to_c(), _lib.ptr(x), _lib.ptr(logw), n, dim, T, self.n_leapfrog_steps, _lib.ptr(betas), _lib.ptr(eps),
             sigma0, inv_var0, None, _lib.ptr(counts), None, None, None, seed, step0, _lib.stream_handle(dev),
         )
