@@ -7,6 +7,7 @@ import functools
 
 import torch
 
+import tempering_cases
 from tempering_cases import TEMPS, energy_spec, model_of, oracle_of  # noqa: F401  (re-exported for the tests)
 
 MARGIN_BAR = 2e-4  # the project's HMC bar on |u - a| (no accept / reject / swap call of the fp64 run may be borderline)
@@ -158,3 +159,42 @@ def case(kind, dim, R, n, swap_every, n_mh):
     ref32 = restate(oracle_of(spec), x0, z, ua, us, eps, L, temps, swap_every, torch.float32, thin=2)
     return {"spec": spec, "temps": temps, "eps": eps, "L": L, "x0": x0, "z": z, "u_accept": ua, "u_swap": us, "ref32": ref32,
             "ref64": ref64, "seed": seed, "shape": (n, R, dim), "n_mh": n_mh, "swap_every": swap_every}
+
+
+# ---------------------------------------------------------------------------------
+# both ladders, states that cannot move: only the swap events act
+# ---------------------------------------------------------------------------------
+FROZEN_EVENTS = 6  # swap_every = 1: both parities, three times each
+
+
+def frozen_masks(c):
+    """Both restatements on the inputs of frozen_case: the Langevin ladder at eta = 0 with zero noise, the HMC ladder at
+    eps = 0 in every slot (dH = 0 exactly, so every proposal -- the unchanged state -- is accepted).  The same u feeds the swaps."""
+    (n, R, dim), energy = c["shape"], oracle_of(c["spec"])
+    lan = tempering_cases.restate(energy, c["x0"], torch.zeros(FROZEN_EVENTS, n, R, dim), c["u"], 0.0, tempering_cases.SIGMA,
+                                  c["temps"], 1, torch.float32)
+    hmc = restate(energy, c["x0"], c["z"], c["u_accept"], c["u"], (0.0,) * R, c["L"], c["temps"], 1, torch.float32)
+    return lan, hmc
+
+
+@functools.lru_cache(maxsize=None)
+def frozen_case(kind, dim, R, n):
+    """Inputs of a run in which no state moves, so the final slot matrix is a permutation of the start made by the swap decisions
+    alone.  The seed is the first at which the Langevin restatement both accepts and rejects swaps.  (sigma = 1: both ladders
+    have beta = 1 / T, rounded once.)"""
+    spec, temps = energy_spec(kind, dim), TEMPS[R]
+    attempts = sum(len(range(m % 2, R - 1, 2)) for m in range(FROZEN_EVENTS)) * n
+    for seed in range(200):
+        x0, z, ua, u = draw_inputs(seed, n, R, dim, FROZEN_EVENTS, 1, 1.0)
+        c = {"spec": spec, "temps": temps, "x0": x0, "z": z, "u_accept": ua, "u": u, "L": 2, "seed": seed, "shape": (n, R, dim),
+             "attempts": attempts}
+        if 0 < int(frozen_masks(c)[0]["mask"].sum()) < attempts:
+            break
+    return c
+
+
+def slot_permutation(x, x0):
+    """perm [n, R] with x[:, r] == x0[:, perm[:, r]] bit for bit; every state of a ladder must be found exactly once."""
+    same = (x[:, :, None, :] == x0[:, None, :, :]).all(dim=-1)  # [n, R now, R at the start]
+    assert (same.sum(dim=-1) == 1).all() and (same.sum(dim=-2) == 1).all(), "a state moved"
+    return same.long().argmax(dim=-1)

@@ -7,7 +7,7 @@ import torch
 
 import torchebm_amd as ta
 from torchebm_amd import _lib
-from tempering_hmc_cases import energy_spec, model_of, oracle_of, restate
+from tempering_hmc_cases import energy_spec, frozen_case, frozen_masks, model_of, oracle_of, restate, slot_permutation
 
 
 def _replay(seed, n, R, dim, n_mh, swap_every):
@@ -62,6 +62,21 @@ def test_eager_gaussian_matches_the_restatement():
     assert not want["accepted"].all() and want["mask"].any()
     got = _sampler(spec, temps, 2, eps, L).sample(x=x0, n_steps=n_mh, return_replicas=True, generator=torch.Generator().manual_seed(seed))
     assert (got - want["x"]).abs().max().item() <= 2e-5
+
+
+@pytest.mark.parametrize("kind,dim,R,n", [("double_well", 5, 3, 37), ("gmm", 32, 4, 37)])
+def test_both_ladders_take_the_same_swap_decisions(kind, dim, R, n):
+    """States that cannot move (Langevin: eta = 0, zero noise; HMC: eps = 0), the same temperatures and the same u: the two
+    restatements decide every swap alike and end with the same permutation of the slots (csrc/ladder.h is one swap event for
+    both kernels; test_tempering_hmc_gpu.py holds the kernels to this)."""
+    c = frozen_case(kind, dim, R, n)
+    lan, hmc = frozen_masks(c)
+    assert 0 < int(lan["mask"].sum()) < c["attempts"], "the case needs accepted and rejected swaps"
+    assert lan["mask"].shape == (6, n, R - 1) and torch.equal(lan["mask"], hmc["mask"])
+    assert hmc["accepted"].all()
+    perm = slot_permutation(lan["x"], c["x0"])
+    assert torch.equal(perm, slot_permutation(hmc["x"], c["x0"])) and torch.equal(lan["x"], hmc["x"])
+    assert (perm != torch.arange(R)).any()
 
 
 def test_diagnostics_of_the_eager_route():

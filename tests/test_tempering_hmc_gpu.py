@@ -8,8 +8,9 @@ import torch
 import torchebm_amd as ta
 from torchebm_amd import _lib, _rng
 from helpers import hip_calls, yardstick
-from tempering_hmc_cases import (CASES, MARGIN_BAR, case, closest_call, energy_spec, ladder, leapfrog_steps, model_of, oracle_of,
-                                 restate, step_sizes)
+import tempering_cases
+from tempering_hmc_cases import (CASES, FROZEN_EVENTS, MARGIN_BAR, case, closest_call, energy_spec, frozen_case, ladder,
+                                 leapfrog_steps, model_of, oracle_of, restate, slot_permutation, step_sizes)
 
 pytestmark = pytest.mark.gpu
 ENTRY = "ebm_tempering_hmc_chain_f32"
@@ -135,6 +136,30 @@ def test_the_transition_is_the_hmc_kernels(cuda_device, dim):
     assert torch.equal(mask.cpu().bool().view(n_mh, n, R), got["accepted"])
     assert (~got["accepted"]).any() and got["accepted"].any()
     assert torch.equal(rows.cpu().view(n, R, dim), got["x"])
+
+
+# unaligned rows and idle lane groups; a G = 32 that is not full; a ladder spread over several waves
+@pytest.mark.parametrize("kind,dim,R,n", [("double_well", 5, 3, 37), ("gmm", 100, 3, 37), ("double_well", 256, 4, 37)])
+def test_both_ladders_take_the_same_swap_decisions(cuda_device, kind, dim, R, n):
+    """States that cannot move, the same temperatures and the same swap uniforms through ebm_tempering_chain_f32 (eta = 0,
+    zero noise) and this entry (eps = 0 in every slot): the same final slot matrix and the same swap counts, bit for bit --
+    both kernels run the one swap event of csrc/ladder.h on energies their evaluations give alike (double well, mixture)."""
+    dev, c, k = cuda_device, frozen_case(kind, dim, R, n), FROZEN_EVENTS
+    x0, u = c["x0"], c["u"]
+    coef, beta = (t.to(dev) for t in tempering_cases.ladder(tempering_cases.SIGMA, c["temps"]))
+    assert torch.equal(beta.cpu(), ladder(c["temps"])[1])
+    x, counts = x0.to(dev).contiguous().clone(), torch.zeros(2 * (R - 1), dtype=torch.int32, device=dev)
+    noise_d, u_d = torch.zeros(k, n, R, dim, device=dev), u.to(dev).contiguous()
+    _lib.call("ebm_tempering_chain_f32", model_of(c["spec"], dev).fused_spec().to_c(), x.data_ptr(), n, R, dim, k, 0.0, 0.0,
+              coef.data_ptr(), beta.data_ptr(), 1, 1, None, counts.data_ptr(), noise_d.data_ptr(), u_d.data_ptr(), 0, 0,
+              _lib.stream_handle(dev))
+    torch.cuda.synchronize()
+    got = run_kernel(dev, c["spec"], x0, c["temps"], (0.0,) * R, c["L"], k, 1, z=c["z"], ua=c["u_accept"], us=u)
+    assert got["accepted"].all(), "dH = 0 exactly: every proposal is taken"
+    assert torch.equal(got["x"], x.cpu())
+    assert torch.equal(got["swaps"], counts.cpu().long())
+    assert 0 < int(got["swaps"][R - 1 :].sum()) < int(got["swaps"][: R - 1].sum()) == c["attempts"]
+    assert (slot_permutation(got["x"], x0) != torch.arange(R)).any()
 
 
 def test_wild_start_stays_in_its_ladder(cuda_device):

@@ -1,17 +1,8 @@
 // Annealed importance sampling (ebm_ais_chain_f32): geometry, refusals and dispatch to the per-energy units
-// (ais_<energy>.hip; the kernel: ais_kernel.h).
+// (ais_unit.hip, one object per kind; the kernel: ais_kernel.h).
 #include "ais_kernel.h"
 
 namespace ebm {
-namespace ais {
-void launch_double_well(const rows::Geometry&, dim3, size_t, hipStream_t, const AisArgs&);
-void launch_harmonic(const rows::Geometry&, dim3, size_t, hipStream_t, const AisArgs&);
-void launch_gaussian(const rows::Geometry&, dim3, size_t, hipStream_t, const AisArgs&);
-void launch_gmm(const rows::Geometry&, dim3, size_t, hipStream_t, const AisArgs&);
-void launch_rosenbrock(const rows::Geometry&, dim3, size_t, hipStream_t, const AisArgs&);
-void launch_ackley(const rows::Geometry&, dim3, size_t, hipStream_t, const AisArgs&);
-void launch_rastrigin(const rows::Geometry&, dim3, size_t, hipStream_t, const AisArgs&);
-}  // namespace ais
 
 // The refusal that depends on the lane geometry (no launch, no device access): ebm_ais_chain_f32 calls this in front of its
 // early return for an empty call, so it needs no GPU.
@@ -38,15 +29,7 @@ int ais_chain_launch(const AisChainReq& q, hipStream_t st) {
   const int64_t blocks = blocks_for(q.n_chains, geo);
   if (blocks > 0x7fffffffLL) return fail(EBM_EINVAL, "%s: too many chains for one launch", who);
   const dim3 grid((unsigned)blocks);
-  switch (q.e.kind) {
-    case EBM_ENERGY_DOUBLE_WELL: ais::launch_double_well(geo, grid, smem, st, a); break;
-    case EBM_ENERGY_HARMONIC:    ais::launch_harmonic(geo, grid, smem, st, a); break;
-    case EBM_ENERGY_GAUSSIAN:    ais::launch_gaussian(geo, grid, smem, st, a); break;
-    case EBM_ENERGY_ROSENBROCK:  ais::launch_rosenbrock(geo, grid, smem, st, a); break;
-    case EBM_ENERGY_ACKLEY:      ais::launch_ackley(geo, grid, smem, st, a); break;
-    case EBM_ENERGY_RASTRIGIN:   ais::launch_rastrigin(geo, grid, smem, st, a); break;
-    default:                     ais::launch_gmm(geo, grid, smem, st, a); break;
-  }
+  for_kind(q.e.kind, [&](auto K) { ais::launch_kind<decltype(K)::value>(geo, grid, smem, st, a); });
   return check_launch(who);
 }
 

@@ -7,7 +7,8 @@
 // labels through LDS; here the temperatures follow each other in time, so a chain never talks to another: no exchange, no
 // barrier in the loop, beta[t] and eps[t] are wave-uniform loads.
 //
-// Transition: the trajectory is hmc::leapfrog_steps<false> of hmc_kernel.h on the PATH energy
+// Transition: ebm_hmc_chain_f32's (hmc_kernel.h: leapfrog_steps<false>, IdentityKinetic, metropolis_accept; the accept uniform is
+// spelled here as hmc_chain_body spells it), on the PATH energy
 //   U_b(x) = (1 - b) E_0(x) + b E(x),   E_0(x) = 0.5 inv_var0 sum x^2
 // which PathEnergy hands it as an Energy of its own around the kind's: one evaluation of the kind's energy gives U and dU/dx,
 // and the adapter keeps E, E_0 and the raw dE/dx of its LAST evaluation -- the proposal's.  Those three are what a chain
@@ -129,10 +130,10 @@ namespace {
 
 extern __shared__ __attribute__((aligned(16))) float ais_smem[];
 
-// One vector per lane (dim <= 256): the geometry of pick_geometry.
-template <int KIND, int G, bool FULL>
+// One vector per lane (dim <= 256), the geometry of pick_geometry: ais_unit.hip builds no other.
+template <int KIND, int G, int NV, bool FULL>
 __global__ __launch_bounds__(kBlock) void ais_chain(AisArgs a) {
-  constexpr int NV = 1;
+  static_assert(NV == 1, "one vector per lane");
   using LaneT = Lane<G, NV, FULL>;
   LaneT L;
   L.init(a.n_chains, a.dim);
@@ -158,16 +159,7 @@ __global__ __launch_bounds__(kBlock) void ais_chain(AisArgs a) {
     }
   }
 
-  // K(p) = 0.5 sum p^2, clamped to [0, 1e10]: the identity-mass form of hmc_chain_body
-  auto kinetic = [&](const Slice<NV>& q) -> float {
-    float acc = 0.0f;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float sq = q.a[0][i] * q.a[0][i];
-      acc += L.ok(0, i) ? sq : 0.0f;
-    }
-    return clamp_nanprop(0.5f * group_sum<G>(acc), 0.0f, 1e10f);
-  };
+  const hmc::IdentityKinetic<LaneT> kinetic{L};
 
   // what the chain carries besides its state: E, E_0 and the raw dE/dx there.  Those of the start come out of the
   // pseudo-transition t = 0 (hmc_kernel.h: zero momentum, zero step size, one leapfrog step, always taken), so the energy is
@@ -231,10 +223,7 @@ __global__ __launch_bounds__(kBlock) void ais_chain(AisArgs a) {
     const float h1 = clamp_nanprop(u1, -1e10f, 1e10f) + kinetic(p);
 
     // ---- Metropolis accept
-    const float dlt = clamp_nanprop(h0 - h1, -50.0f, 50.0f);
-    float acc_p = expf(dlt);
-    acc_p = (acc_p > 1.0f) ? 1.0f : acc_p;  // NaN stays NaN and rejects
-    const bool accept = init || (L.active && (uu < acc_p));
+    const bool accept = hmc::metropolis_accept(h0 - h1, uu, init, L.active);
     if (accept) {  // the proposal's parts become the carried ones
       xc = x;
       e_cur = path.e_tgt;
@@ -253,21 +242,11 @@ __global__ __launch_bounds__(kBlock) void ais_chain(AisArgs a) {
   if (leader) a.logw[L.chain] = lw;
 }
 
-template <int KIND>
-void launch_kind(const Geometry& geo, dim3 grid, size_t smem, hipStream_t st, const AisArgs& a) {
-  const dim3 block(kBlock);
-#define EBM_AIS_G(GV)                                                                          \
-  case GV:                                                                                     \
-    if (geo.full) hipLaunchKernelGGL((ais_chain<KIND, GV, true>), grid, block, smem, st, a);   \
-    else hipLaunchKernelGGL((ais_chain<KIND, GV, false>), grid, block, smem, st, a);           \
-    break;
-  switch (geo.G) {
-    EBM_AIS_G(1) EBM_AIS_G(2) EBM_AIS_G(4) EBM_AIS_G(8) EBM_AIS_G(16) EBM_AIS_G(32) EBM_AIS_G(64)
-  }
-#undef EBM_AIS_G
-}
-
 }  // namespace
+
+// The launcher of one energy kind: defined and instantiated in ais_unit.hip (one object per kind).
+template <int KIND>
+void launch_kind(const Geometry& geo, dim3 grid, size_t smem, hipStream_t st, const AisArgs& a);
 
 }  // namespace ais
 }  // namespace ebm

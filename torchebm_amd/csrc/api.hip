@@ -142,6 +142,18 @@ int check_state(const void* x, int64_t n_chains, int32_t dim, const char* who) {
   return 0;
 }
 
+// What the two replica-exchange entries check alike: the energy kind and the slot matrix [n_ladders * n_replicas, dim]
+int check_ladders(const ebm_energy_t* energy, const void* x, int64_t n_ladders, int32_t n_replicas, int32_t dim, const char* who) {
+  if (energy && energy->kind == EBM_ENERGY_MLP)
+    return fail(EBM_EKIND, "%s: the MLP energy has no replica-exchange kernel (the sampler's eager route takes it)", who);
+  if (int r = check_energy(energy, dim, who)) return r;
+  if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
+  if (n_replicas < 2 || n_replicas > 64) return fail(EBM_EINVAL, "%s: n_replicas=%d (a ladder has 2 .. 64 slots)", who, n_replicas);
+  if (n_ladders < 0 || dim < 1) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d, %d]", who, (long long)n_ladders, n_replicas, dim);
+  if (!aligned16(x)) return fail(EBM_EINVAL, "%s: state pointer must be 16-byte aligned", who);
+  return 0;
+}
+
 // ebm_langevin_chain_from_f32 on a kernel family that updates in place: the start state goes into the output first
 int copy_state(float* x, const float* src, size_t bytes, hipStream_t st, const char* who) {
   const hipError_t e = hipMemcpyAsync(x, src, bytes, hipMemcpyDeviceToDevice, st);
@@ -407,13 +419,7 @@ int ebm_tempering_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_ladd
                             int32_t swap_every, int32_t thin, float* traj, uint32_t* swap_counts, const float* noise,
                             const float* u, uint64_t seed, uint64_t step0, void* stream) {
   const char* who = "ebm_tempering_chain_f32";
-  if (energy && energy->kind == EBM_ENERGY_MLP)
-    return fail(EBM_EKIND, "%s: the MLP energy has no replica-exchange kernel (the sampler's eager route takes it)", who);
-  if (int r = check_energy(energy, dim, who)) return r;
-  if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
-  if (n_replicas < 2 || n_replicas > 64) return fail(EBM_EINVAL, "%s: n_replicas=%d (a ladder has 2 .. 64 slots)", who, n_replicas);
-  if (n_ladders < 0 || dim < 1) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d, %d]", who, (long long)n_ladders, n_replicas, dim);
-  if (!aligned16(x)) return fail(EBM_EINVAL, "%s: state pointer must be 16-byte aligned", who);
+  if (int r = check_ladders(energy, x, n_ladders, n_replicas, dim, who)) return r;
   if (k_steps < 0 || swap_every < 1 || thin < 1)
     return fail(EBM_EINVAL, "%s: k_steps=%d swap_every=%d thin=%d", who, k_steps, swap_every, thin);
   if (int r = tempering_check_geometry(n_replicas, dim)) return r;
@@ -432,13 +438,7 @@ int ebm_tempering_hmc_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_
                                 uint32_t* swap_counts, const float* p_noise, const float* u_accept, const float* u_swap,
                                 uint64_t seed, uint64_t step0, void* stream) {
   const char* who = "ebm_tempering_hmc_chain_f32";
-  if (energy && energy->kind == EBM_ENERGY_MLP)
-    return fail(EBM_EKIND, "%s: the MLP energy has no replica-exchange kernel (the sampler's eager route takes it)", who);
-  if (int r = check_energy(energy, dim, who)) return r;
-  if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
-  if (n_replicas < 2 || n_replicas > 64) return fail(EBM_EINVAL, "%s: n_replicas=%d (a ladder has 2 .. 64 slots)", who, n_replicas);
-  if (n_ladders < 0 || dim < 1) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d, %d]", who, (long long)n_ladders, n_replicas, dim);
-  if (!aligned16(x)) return fail(EBM_EINVAL, "%s: state pointer must be 16-byte aligned", who);
+  if (int r = check_ladders(energy, x, n_ladders, n_replicas, dim, who)) return r;
   if (n_mh < 0 || n_leapfrog < 1 || swap_every < 1 || thin < 1)
     return fail(EBM_EINVAL, "%s: n_mh=%d n_leapfrog=%d swap_every=%d thin=%d", who, n_mh, n_leapfrog, swap_every, thin);
   if (int r = tempering_hmc_check_geometry(n_replicas, dim)) return r;
@@ -452,50 +452,50 @@ int ebm_tempering_hmc_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_
   return tempering_hmc_chain_launch(q, (hipStream_t)stream);
 }
 
-int ebm_ais_chain_f32(const ebm_energy_t* energy, float* x, float* logw, int64_t n_chains, int32_t dim, int32_t n_temps,
-                      int32_t n_leapfrog, const float* beta, const float* eps, float sigma0, float inv_var0, uint8_t* accept_mask,
-                      uint32_t* accept_counts, const float* x0, const float* p_noise, const float* u_accept, uint64_t seed,
-                      uint64_t step0, void* stream) {
-  const char* who = "ebm_ais_chain_f32";
-  if (energy && energy->kind == EBM_ENERGY_MLP)
+// Both annealed-importance-sampling entries: the analytic kinds on the lane-group kernel, the MLP energy on the matrix cores
+static int ais_chain_impl(const char* who, bool mlp, const ebm_energy_t* energy, float* x, float* logw, int64_t n_chains, int32_t dim,
+                          int32_t n_temps, int32_t n_leapfrog, const float* beta, const float* eps, float sigma0, float inv_var0,
+                          uint8_t* accept_mask, uint32_t* accept_counts, const float* x0, const float* p_noise, const float* u_accept,
+                          uint64_t seed, uint64_t step0, void* stream) {
+  if (!mlp && energy && energy->kind == EBM_ENERGY_MLP)
     return fail(EBM_EKIND, "%s: the MLP energy has no annealed-importance-sampling kernel (the sampler's eager route takes it)", who);
   if (int r = check_energy(energy, dim, who)) return r;
-  if (int r = check_state(x, n_chains, dim, who)) return r;
+  if (mlp && energy->kind != EBM_ENERGY_MLP)
+    return fail(EBM_EKIND, "%s: this entry walks the MLP energy only (ebm_ais_chain_f32 takes the analytic kinds)", who);
+  if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
+  // (the MLP walk's dim range is ais_mlp_check_shape's to refuse)
+  if (n_chains < 0 || (!mlp && dim < 1)) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d]", who, (long long)n_chains, dim);
+  if (!aligned16(x)) return fail(EBM_EINVAL, "%s: state pointer must be 16-byte aligned", who);
   if (!logw) return fail(EBM_EINVAL, "%s: logw is NULL", who);
   if (n_temps < 1 || n_leapfrog < 1) return fail(EBM_EINVAL, "%s: n_temps=%d n_leapfrog=%d", who, n_temps, n_leapfrog);
-  if (int r = ais_check_geometry(dim)) return r;
+  if (!mlp)
+    if (int r = ais_check_geometry(dim)) return r;
   if (!beta || !eps) return fail(EBM_EINVAL, "%s: beta / eps is NULL", who);
   if ((x0 == nullptr) != (p_noise == nullptr) || (x0 == nullptr) != (u_accept == nullptr))
     return fail(EBM_EINVAL, "%s: x0, p_noise and u_accept must be given together", who);
+  if (mlp)
+    if (int r = ais_mlp_check_shape(energy->n_comp, dim)) return r;
   if (n_chains == 0) return 0;
   if ((x0 && !aligned16(x0)) || (p_noise && !aligned16(p_noise))) return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
   const AisChainReq q{*energy, x, logw, n_chains, dim, n_temps, n_leapfrog, beta, eps, sigma0, inv_var0, accept_mask, accept_counts,
                       x0, p_noise, u_accept, seed, step0};
-  return ais_chain_launch(q, (hipStream_t)stream);
+  return mlp ? ais_mlp_chain_launch(q, (hipStream_t)stream) : ais_chain_launch(q, (hipStream_t)stream);
+}
+
+int ebm_ais_chain_f32(const ebm_energy_t* energy, float* x, float* logw, int64_t n_chains, int32_t dim, int32_t n_temps,
+                      int32_t n_leapfrog, const float* beta, const float* eps, float sigma0, float inv_var0, uint8_t* accept_mask,
+                      uint32_t* accept_counts, const float* x0, const float* p_noise, const float* u_accept, uint64_t seed,
+                      uint64_t step0, void* stream) {
+  return ais_chain_impl("ebm_ais_chain_f32", false, energy, x, logw, n_chains, dim, n_temps, n_leapfrog, beta, eps, sigma0, inv_var0,
+                        accept_mask, accept_counts, x0, p_noise, u_accept, seed, step0, stream);
 }
 
 int ebm_ais_mlp_chain_f32(const ebm_energy_t* energy, float* x, float* logw, int64_t n_chains, int32_t dim, int32_t n_temps,
                           int32_t n_leapfrog, const float* beta, const float* eps, float sigma0, float inv_var0, uint8_t* accept_mask,
                           uint32_t* accept_counts, const float* x0, const float* p_noise, const float* u_accept, uint64_t seed,
                           uint64_t step0, void* stream) {
-  const char* who = "ebm_ais_mlp_chain_f32";
-  if (int r = check_energy(energy, dim, who)) return r;
-  if (energy->kind != EBM_ENERGY_MLP)
-    return fail(EBM_EKIND, "%s: this entry walks the MLP energy only (ebm_ais_chain_f32 takes the analytic kinds)", who);
-  if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
-  if (!logw) return fail(EBM_EINVAL, "%s: logw is NULL", who);
-  if (n_chains < 0) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d]", who, (long long)n_chains, dim);
-  if (n_temps < 1 || n_leapfrog < 1) return fail(EBM_EINVAL, "%s: n_temps=%d n_leapfrog=%d", who, n_temps, n_leapfrog);
-  if (!beta || !eps) return fail(EBM_EINVAL, "%s: beta / eps is NULL", who);
-  if ((x0 == nullptr) != (p_noise == nullptr) || (x0 == nullptr) != (u_accept == nullptr))
-    return fail(EBM_EINVAL, "%s: x0, p_noise and u_accept must be given together", who);
-  if (int r = ais_mlp_check_shape(energy->n_comp, dim)) return r;
-  if (!aligned16(x)) return fail(EBM_EINVAL, "%s: state pointer must be 16-byte aligned", who);
-  if (n_chains == 0) return 0;
-  if ((x0 && !aligned16(x0)) || (p_noise && !aligned16(p_noise))) return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
-  const AisChainReq q{*energy, x, logw, n_chains, dim, n_temps, n_leapfrog, beta, eps, sigma0, inv_var0, accept_mask, accept_counts,
-                      x0, p_noise, u_accept, seed, step0};
-  return ais_mlp_chain_launch(q, (hipStream_t)stream);
+  return ais_chain_impl("ebm_ais_mlp_chain_f32", true, energy, x, logw, n_chains, dim, n_temps, n_leapfrog, beta, eps, sigma0, inv_var0,
+                        accept_mask, accept_counts, x0, p_noise, u_accept, seed, step0, stream);
 }
 
 int ebm_leapfrog_kick_drift_f32(const float* x, const float* p, const float* force, float* x_new,

@@ -11,22 +11,7 @@ namespace ebm {
 using namespace rows;
 
 namespace hmc {
-// one definition per energy, each in its own translation unit
-void launch_double_well(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
-void launch_harmonic(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
-void launch_gaussian(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
-void launch_gmm(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
-void launch_rosenbrock(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
-void launch_ackley(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
-void launch_rastrigin(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
-// ... and the variants that emit diagnostics records at the kept transitions (hmc_*_diag.hip)
-void launch_double_well_diag(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
-void launch_harmonic_diag(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
-void launch_gaussian_diag(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
-void launch_gmm_diag(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
-void launch_rosenbrock_diag(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
-void launch_ackley_diag(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
-void launch_rastrigin_diag(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
+// (launch_kind<KIND, DIAG>: hmc_kernel.h, one object per energy kind and form from hmc_unit.hip)
 // hmc_literal.hip: the audit form for the element-wise energies (ebm_hmc_chain_audit_f32)
 void launch_literal_double_well(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
 void launch_literal_harmonic(const rows::Geometry&, dim3, size_t, hipStream_t, const HmcArgs&);
@@ -174,27 +159,8 @@ int launch_hmc_chain(const HmcChainReq& q, hipStream_t st) {
     hmc::launch_gmm32(grid, st, a);
     return check_launch("ebm_hmc_chain_f32");
   }
-  if (diag_kernel) {
-    switch (e.kind) {
-      case EBM_ENERGY_DOUBLE_WELL: hmc::launch_double_well_diag(geo, grid, smem, st, a); break;
-      case EBM_ENERGY_HARMONIC:    hmc::launch_harmonic_diag(geo, grid, smem, st, a); break;
-      case EBM_ENERGY_GAUSSIAN:    hmc::launch_gaussian_diag(geo, grid, smem, st, a); break;
-      case EBM_ENERGY_ROSENBROCK:  hmc::launch_rosenbrock_diag(geo, grid, smem, st, a); break;
-      case EBM_ENERGY_ACKLEY:      hmc::launch_ackley_diag(geo, grid, smem, st, a); break;
-      case EBM_ENERGY_RASTRIGIN:   hmc::launch_rastrigin_diag(geo, grid, smem, st, a); break;
-      default:                     hmc::launch_gmm_diag(geo, grid, smem, st, a); break;
-    }
-    return check_launch("ebm_hmc_chain_f32");
-  }
-  switch (e.kind) {
-    case EBM_ENERGY_DOUBLE_WELL: hmc::launch_double_well(geo, grid, smem, st, a); break;
-    case EBM_ENERGY_HARMONIC:    hmc::launch_harmonic(geo, grid, smem, st, a); break;
-    case EBM_ENERGY_GAUSSIAN:    hmc::launch_gaussian(geo, grid, smem, st, a); break;
-    case EBM_ENERGY_ROSENBROCK:  hmc::launch_rosenbrock(geo, grid, smem, st, a); break;
-    case EBM_ENERGY_ACKLEY:      hmc::launch_ackley(geo, grid, smem, st, a); break;
-    case EBM_ENERGY_RASTRIGIN:   hmc::launch_rastrigin(geo, grid, smem, st, a); break;
-    default:                     hmc::launch_gmm(geo, grid, smem, st, a); break;
-  }
+  if (diag_kernel) for_kind(e.kind, [&](auto K) { hmc::launch_kind<decltype(K)::value, true>(geo, grid, smem, st, a); });
+  else for_kind(e.kind, [&](auto K) { hmc::launch_kind<decltype(K)::value, false>(geo, grid, smem, st, a); });
   return check_launch("ebm_hmc_chain_f32");
 }
 

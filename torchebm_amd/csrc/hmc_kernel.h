@@ -1,5 +1,5 @@
-// HMC transition kernel template (included by the per-energy translation units hmc_*.hip, which
-// only exist so that the energies compile in parallel).  See hmc.hip for the entry point.
+// HMC transition kernel template.  hmc_unit.hip instantiates it, compiled once per energy kind so that the energies build in
+// parallel (Makefile: KIND_UNITS).  See hmc.hip for the entry point.
 #pragma once
 #include "rows.h"
 
@@ -182,6 +182,37 @@ __device__ __forceinline__ float leapfrog_steps(const En& en, const LaneT& L, Sl
     }
   }
   return e;
+}
+
+// ---- the arithmetic around a trajectory that the tempered kernels share (tempering_hmc_kernel.h, ais_kernel.h).
+//      hmc_chain_body below spells the same Metropolis decision in place, operation for operation
+//      (tests/test_tempering_hmc_gpu.py test_the_transition_is_the_hmc_kernels and tests/test_ais_gpu.py hold them together).
+
+// K(p) = 0.5 sum p^2 over the group's row, clamped to [0, 1e10]: the identity-mass kinetic energy of the lane L.
+// `const hmc::IdentityKinetic<LaneT> kinetic{L};` in the kernel, then kinetic(p) -- a closure, as the lambda of hmc_chain_body is.
+template <class LaneT>
+struct IdentityKinetic {
+  const LaneT& L;
+  __device__ __forceinline__ float operator()(const Slice<LaneT::NV>& q) const {
+    float acc = 0.0f;
+#pragma unroll
+    for (int v = 0; v < LaneT::NV; ++v)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float sq = q.a[v][i] * q.a[v][i];
+        acc += L.ok(v, i) ? sq : 0.0f;
+      }
+    return clamp_nanprop(0.5f * group_sum<LaneT::G>(acc), 0.0f, 1e10f);
+  }
+};
+
+// The Metropolis decision from dH = H0 - H1 (samplers/hmc.py:277-292): clamp to [-50, 50], exp, clamp_(max=1); NaN stays
+// NaN and rejects.  The pseudo-transition always takes its "proposal": the unchanged state with its energy and force.
+__device__ __forceinline__ bool metropolis_accept(float dH, float uu, bool init, bool active) {
+  const float dlt = clamp_nanprop(dH, -50.0f, 50.0f);
+  float acc_p = expf(dlt);
+  acc_p = (acc_p > 1.0f) ? 1.0f : acc_p;
+  return init || (active && (uu < acc_p));
 }
 
 // The AUDIT form of the trajectory (ebm_hmc_chain_audit_f32; tests only): the reference's safe-mode leapfrog step literally
@@ -535,74 +566,10 @@ __global__ __launch_bounds__(kBlock, 2) void hmc_chain_kernel_w2(HmcArgs a) {
   hmc_chain_body<KIND, G, NV, FULL, MASS, DIAG, true>(a);
 }
 
-// KERNEL<KIND, G, NV, FULL, MASS, DIAG> over the runtime geometry (see rows.h: EBM_GEO_LAUNCH)
-template <int KIND, int MASS, bool DIAG>
-void launch_geo(const Geometry& geo, dim3 grid, size_t smem, hipStream_t st, const HmcArgs& a) {
-  const dim3 block(kBlock);
-#define EBM_HMC_G(GV, NVV, FULLV) hipLaunchKernelGGL((hmc_chain_kernel<KIND, GV, NVV, FULLV, MASS, DIAG>), grid, block, smem, st, a)
-  if (geo.NV == 1) {
-    switch (geo.G) {
-      case 1:  if (geo.full) EBM_HMC_G(1, 1, true);  else EBM_HMC_G(1, 1, false);  break;
-      case 2:  if (geo.full) EBM_HMC_G(2, 1, true);  else EBM_HMC_G(2, 1, false);  break;
-      case 4:  if (geo.full) EBM_HMC_G(4, 1, true);  else EBM_HMC_G(4, 1, false);  break;
-      case 8:  if (geo.full) EBM_HMC_G(8, 1, true);  else EBM_HMC_G(8, 1, false);  break;
-      case 16: if (geo.full) EBM_HMC_G(16, 1, true); else EBM_HMC_G(16, 1, false); break;
-      case 32: if (geo.full) EBM_HMC_G(32, 1, true); else EBM_HMC_G(32, 1, false); break;
-      default: if (geo.full) EBM_HMC_G(64, 1, true); else EBM_HMC_G(64, 1, false); break;
-    }
-  } else if (geo.NV == 3) {  // element-wise energies, row widths in (2^k, 1.5 2^k] vectors: three vectors per lane (hmc.hip: hmc_geometry)
-    if constexpr (KIND == EBM_ENERGY_DOUBLE_WELL || KIND == EBM_ENERGY_HARMONIC) {
-      switch (geo.G) {
-        case 1:  EBM_HMC_G(1, 3, false);  break;
-        case 2:  EBM_HMC_G(2, 3, false);  break;
-        case 4:  EBM_HMC_G(4, 3, false);  break;
-        case 8:  EBM_HMC_G(8, 3, false);  break;
-        case 16: EBM_HMC_G(16, 3, false); break;
-        case 32: EBM_HMC_G(32, 3, false); break;
-        default: EBM_HMC_G(64, 3, false); break;
-      }
-    }
-  } else if (geo.G == 64 && geo.NV == 2) {
-    // (element-wise energies at exactly 512 / 1024 dims: the full-row form -- no per-element masks)
-    if constexpr (KIND == EBM_ENERGY_DOUBLE_WELL || KIND == EBM_ENERGY_HARMONIC) {
-      if (geo.full) EBM_HMC_G(64, 2, true);
-      else EBM_HMC_G(64, 2, false);
-    } else {
-      EBM_HMC_G(64, 2, false);
-    }
-  } else if (geo.G == 64 && geo.NV == 4) {
-    if constexpr (KIND == EBM_ENERGY_DOUBLE_WELL || KIND == EBM_ENERGY_HARMONIC) {
-      if (geo.full) EBM_HMC_G(64, 4, true);
-      else EBM_HMC_G(64, 4, false);
-    } else {
-      EBM_HMC_G(64, 4, false);
-    }
-  } else if (geo.NV == 4 && geo.full && (geo.G == 4 || geo.G == 8)) {  // element-wise energies at dim 64 / 128
-    if constexpr (KIND == EBM_ENERGY_DOUBLE_WELL || KIND == EBM_ENERGY_HARMONIC) {
-      if (geo.G == 4) EBM_HMC_G(4, 4, true);
-      else EBM_HMC_G(8, 4, true);
-    }
-  } else if constexpr (KIND >= EBM_ENERGY_ROSENBROCK) {
-    // the landscape kinds keep the geometries of pick_geometry: hmc.hip hmc_geometry offers them no dim-32 alternative
-  } else if (geo.G == 4 && geo.NV == 2) {  // dim-32 alternatives (full rows only)
-    EBM_HMC_G(4, 2, true);
-  } else if (geo.G == 2 && geo.NV == 4) {
-    EBM_HMC_G(2, 4, true);
-  } else if constexpr (KIND == EBM_ENERGY_GMM) {
-    // (1, 8) is the small-mixture geometry (K <= 8 at dim 32, hmc.hip: hmc_geometry); with identity mass those calls never get
-    // here -- hmc_ring.hip / hmc_gmm32.hip serve them, records included -- so only the massed form is instantiated
-    if constexpr (MASS != 0) hipLaunchKernelGGL((hmc_chain_kernel_w2<KIND, 1, 8, true, MASS, DIAG>), grid, block, smem, st, a);
-  } else {
-    EBM_HMC_G(1, 8, true);
-  }
-#undef EBM_HMC_G
-}
-
+// The launcher of one energy kind, without / with the diagnostics records: defined and instantiated in hmc_unit.hip (one
+// object per kind and form), so a unit that only calls it compiles no kernel.
 template <int KIND, bool DIAG>
-void launch_kind(const Geometry& geo, dim3 grid, size_t smem, hipStream_t st, const HmcArgs& a) {
-  if (a.mass_kind == EBM_MASS_NONE) launch_geo<KIND, 0, DIAG>(geo, grid, smem, st, a);
-  else launch_geo<KIND, 1, DIAG>(geo, grid, smem, st, a);
-}
+void launch_kind(const Geometry& geo, dim3 grid, size_t smem, hipStream_t st, const HmcArgs& a);
 
 }  // namespace hmc
 }  // namespace ebm

@@ -1,7 +1,8 @@
 // The three test landscapes of the reference's core as lane-group energies (rows.h: Energy<KIND, LaneT>):
 // Rosenbrock (base_model.py:232-264), Ackley (:267-294), Rastrigin (:297-316).  Scalars only, no LDS.
-// A header of its own, included after rows.h by the units that instantiate these kinds (rows_langevin.hip and
-// hmc_<energy>[_diag].hip), so that every other unit compiles from the text it had.  docs/design/landscapes.md.
+// A header of its own, included after rows.h by the units that instantiate these kinds (rows_langevin.hip and the per-kind
+// units, *_unit.hip: one source serves every kind, so all its objects see this text and only the landscape kinds' objects
+// instantiate it), so that every other unit compiles from the text it had.  docs/design/landscapes.md.
 //
 // The contract of rows.h holds here as there: slots with !L.ok(v, i) hold x = 0, must return g = 0 and add nothing to
 // the energy.  It bites three times: cos(0) = 1 (a padded slot would add -a to Rastrigin's sum and 1 to Ackley's mean

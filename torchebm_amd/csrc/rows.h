@@ -15,6 +15,8 @@
 // validity selects disappear from the inner loops; lanes of chains past n_chains then
 // compute on zeros and are only prevented from loading/storing.
 #pragma once
+#include <type_traits>
+
 #include "diag.h"
 #include "ebm_common.h"
 
@@ -1024,11 +1026,10 @@ inline int64_t blocks_for(int64_t n_chains, const Geometry& geo) {
   return ceil_div64(n_chains, kBlock / geo.G);
 }
 
-// KERNEL<KIND, G, NV, FULL> dispatch.  FULL variants exist for NV == 1 only (dim <= 256);
-// larger rows always carry their validity mask.
-#define EBM_GEO_LAUNCH(KERNEL, KIND, geo, ...)                                                   \
+// KERNEL<KIND, G, 1, FULL> dispatch: one vector per lane (dim <= 256), for the kernels that exist in that form only
+#define EBM_GEO_LAUNCH_NV1(KERNEL, KIND, geo, ...)                                               \
   do {                                                                                           \
-    if (geo.NV == 1 && geo.full) {                                                               \
+    if (geo.full) {                                                                              \
       switch (geo.G) {                                                                           \
         case 1:  hipLaunchKernelGGL((KERNEL<KIND, 1, 1, true>), __VA_ARGS__); break;             \
         case 2:  hipLaunchKernelGGL((KERNEL<KIND, 2, 1, true>), __VA_ARGS__); break;             \
@@ -1038,7 +1039,7 @@ inline int64_t blocks_for(int64_t n_chains, const Geometry& geo) {
         case 32: hipLaunchKernelGGL((KERNEL<KIND, 32, 1, true>), __VA_ARGS__); break;            \
         default: hipLaunchKernelGGL((KERNEL<KIND, 64, 1, true>), __VA_ARGS__); break;            \
       }                                                                                          \
-    } else if (geo.NV == 1) {                                                                    \
+    } else {                                                                                     \
       switch (geo.G) {                                                                           \
         case 1:  hipLaunchKernelGGL((KERNEL<KIND, 1, 1, false>), __VA_ARGS__); break;            \
         case 2:  hipLaunchKernelGGL((KERNEL<KIND, 2, 1, false>), __VA_ARGS__); break;            \
@@ -1048,6 +1049,15 @@ inline int64_t blocks_for(int64_t n_chains, const Geometry& geo) {
         case 32: hipLaunchKernelGGL((KERNEL<KIND, 32, 1, false>), __VA_ARGS__); break;           \
         default: hipLaunchKernelGGL((KERNEL<KIND, 64, 1, false>), __VA_ARGS__); break;           \
       }                                                                                          \
+    }                                                                                            \
+  } while (0)
+
+// KERNEL<KIND, G, NV, FULL> dispatch.  FULL variants exist for NV == 1 only (dim <= 256);
+// larger rows always carry their validity mask.
+#define EBM_GEO_LAUNCH(KERNEL, KIND, geo, ...)                                                   \
+  do {                                                                                           \
+    if (geo.NV == 1) {                                                                           \
+      EBM_GEO_LAUNCH_NV1(KERNEL, KIND, geo, __VA_ARGS__);                                        \
     } else if (geo.NV == 2) {                                                                    \
       hipLaunchKernelGGL((KERNEL<KIND, 64, 2, false>), __VA_ARGS__);                             \
     } else {                                                                                     \
@@ -1055,19 +1065,26 @@ inline int64_t blocks_for(int64_t n_chains, const Geometry& geo) {
     }                                                                                            \
   } while (0)
 
+// The one switch over the energy kinds of the lane-group kernels: f(kind_c<KIND>{}) with the runtime kind as a constant
+// (decltype(K)::value inside a generic lambda).  Anything that is none of the others is the mixture, as ever.
+template <int KIND>
+using kind_c = std::integral_constant<int, KIND>;
+template <class F>
+inline void for_kind(int kind, F&& f) {
+  switch (kind) {
+    case EBM_ENERGY_DOUBLE_WELL: f(kind_c<EBM_ENERGY_DOUBLE_WELL>{}); break;
+    case EBM_ENERGY_HARMONIC:    f(kind_c<EBM_ENERGY_HARMONIC>{}); break;
+    case EBM_ENERGY_GAUSSIAN:    f(kind_c<EBM_ENERGY_GAUSSIAN>{}); break;
+    case EBM_ENERGY_ROSENBROCK:  f(kind_c<EBM_ENERGY_ROSENBROCK>{}); break;
+    case EBM_ENERGY_ACKLEY:      f(kind_c<EBM_ENERGY_ACKLEY>{}); break;
+    case EBM_ENERGY_RASTRIGIN:   f(kind_c<EBM_ENERGY_RASTRIGIN>{}); break;
+    default:                     f(kind_c<EBM_ENERGY_GMM>{}); break;
+  }
+}
+
 // (the landscape kinds: csrc/landscape_energies.h, which a unit that expands this macro includes after rows.h)
-#define EBM_KIND_LAUNCH(KERNEL, kind, geo, ...)                                                  \
-  do {                                                                                           \
-    switch (kind) {                                                                              \
-      case EBM_ENERGY_DOUBLE_WELL: EBM_GEO_LAUNCH(KERNEL, EBM_ENERGY_DOUBLE_WELL, geo, __VA_ARGS__); break; \
-      case EBM_ENERGY_HARMONIC:    EBM_GEO_LAUNCH(KERNEL, EBM_ENERGY_HARMONIC, geo, __VA_ARGS__); break;    \
-      case EBM_ENERGY_GAUSSIAN:    EBM_GEO_LAUNCH(KERNEL, EBM_ENERGY_GAUSSIAN, geo, __VA_ARGS__); break;    \
-      case EBM_ENERGY_ROSENBROCK:  EBM_GEO_LAUNCH(KERNEL, EBM_ENERGY_ROSENBROCK, geo, __VA_ARGS__); break;  \
-      case EBM_ENERGY_ACKLEY:      EBM_GEO_LAUNCH(KERNEL, EBM_ENERGY_ACKLEY, geo, __VA_ARGS__); break;      \
-      case EBM_ENERGY_RASTRIGIN:   EBM_GEO_LAUNCH(KERNEL, EBM_ENERGY_RASTRIGIN, geo, __VA_ARGS__); break;   \
-      default:                     EBM_GEO_LAUNCH(KERNEL, EBM_ENERGY_GMM, geo, __VA_ARGS__); break;         \
-    }                                                                                            \
-  } while (0)
+#define EBM_KIND_LAUNCH(KERNEL, kind, geo, ...) \
+  for_kind(kind, [&](auto K) { EBM_GEO_LAUNCH(KERNEL, decltype(K)::value, geo, __VA_ARGS__); })
 
 }  // namespace rows
 }  // namespace ebm

@@ -1,17 +1,8 @@
 // Replica-exchange Langevin (ebm_tempering_chain_f32): geometry, refusals and dispatch to the per-energy units
-// (tempering_<energy>.hip; the kernel: tempering_kernel.h).
+// (tempering_unit.hip, one object per kind; the kernel: tempering_kernel.h).
 #include "tempering_kernel.h"
 
 namespace ebm {
-namespace tempering {
-void launch_double_well(const rows::Geometry&, dim3, size_t, hipStream_t, const TemperArgs&);
-void launch_harmonic(const rows::Geometry&, dim3, size_t, hipStream_t, const TemperArgs&);
-void launch_gaussian(const rows::Geometry&, dim3, size_t, hipStream_t, const TemperArgs&);
-void launch_gmm(const rows::Geometry&, dim3, size_t, hipStream_t, const TemperArgs&);
-void launch_rosenbrock(const rows::Geometry&, dim3, size_t, hipStream_t, const TemperArgs&);
-void launch_ackley(const rows::Geometry&, dim3, size_t, hipStream_t, const TemperArgs&);
-void launch_rastrigin(const rows::Geometry&, dim3, size_t, hipStream_t, const TemperArgs&);
-}  // namespace tempering
 
 // The refusals that depend on the lane geometry (no launch, no device access): ebm_tempering_chain_f32 calls this in front
 // of its early return for an empty call, so they need no GPU.
@@ -38,21 +29,10 @@ int tempering_chain_launch(const TemperingChainReq& q, hipStream_t st) {
   a.noise = q.noise; a.u = q.u; a.key = q.key(); a.step0 = q.offset;
   size_t smem = 0;
   plan_params(q.e, q.dim, geo, a.energy, a.param_floats, smem);
-  a.table_offset_floats = (int)(smem / sizeof(float));
-  smem += (size_t)(kBlock / geo.G) * sizeof(float);  // the energy table: one float per lane group
-  const int lpb = (kBlock / geo.G) / q.n_replicas;
-  const int64_t blocks = ceil_div64(q.n_ladders, lpb);
+  const int64_t blocks = ladder::plan(geo, q.n_replicas, q.n_ladders, smem, a.table_offset_floats);
   if (blocks > 0x7fffffffLL) return fail(EBM_EINVAL, "%s: too many ladders for one launch", who);
   const dim3 grid((unsigned)blocks);
-  switch (q.e.kind) {
-    case EBM_ENERGY_DOUBLE_WELL: tempering::launch_double_well(geo, grid, smem, st, a); break;
-    case EBM_ENERGY_HARMONIC:    tempering::launch_harmonic(geo, grid, smem, st, a); break;
-    case EBM_ENERGY_GAUSSIAN:    tempering::launch_gaussian(geo, grid, smem, st, a); break;
-    case EBM_ENERGY_ROSENBROCK:  tempering::launch_rosenbrock(geo, grid, smem, st, a); break;
-    case EBM_ENERGY_ACKLEY:      tempering::launch_ackley(geo, grid, smem, st, a); break;
-    case EBM_ENERGY_RASTRIGIN:   tempering::launch_rastrigin(geo, grid, smem, st, a); break;
-    default:                     tempering::launch_gmm(geo, grid, smem, st, a); break;
-  }
+  for_kind(q.e.kind, [&](auto K) { tempering::launch_kind<decltype(K)::value>(geo, grid, smem, st, a); });
   return check_launch(who);
 }
 

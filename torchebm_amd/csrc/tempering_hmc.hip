@@ -1,17 +1,8 @@
 // Replica-exchange HMC (ebm_tempering_hmc_chain_f32): geometry, refusals and dispatch to the per-energy units
-// (tempering_hmc_<energy>.hip; the kernel: tempering_hmc_kernel.h).
+// (tempering_hmc_unit.hip, one object per kind; the kernel: tempering_hmc_kernel.h).
 #include "tempering_hmc_kernel.h"
 
 namespace ebm {
-namespace tempering_hmc {
-void launch_double_well(const rows::Geometry&, dim3, size_t, hipStream_t, const TemperHmcArgs&);
-void launch_harmonic(const rows::Geometry&, dim3, size_t, hipStream_t, const TemperHmcArgs&);
-void launch_gaussian(const rows::Geometry&, dim3, size_t, hipStream_t, const TemperHmcArgs&);
-void launch_gmm(const rows::Geometry&, dim3, size_t, hipStream_t, const TemperHmcArgs&);
-void launch_rosenbrock(const rows::Geometry&, dim3, size_t, hipStream_t, const TemperHmcArgs&);
-void launch_ackley(const rows::Geometry&, dim3, size_t, hipStream_t, const TemperHmcArgs&);
-void launch_rastrigin(const rows::Geometry&, dim3, size_t, hipStream_t, const TemperHmcArgs&);
-}  // namespace tempering_hmc
 
 // The refusals that depend on the lane geometry (no launch, no device access): ebm_tempering_hmc_chain_f32 calls this in
 // front of its early return for an empty call, so they need no GPU.
@@ -40,22 +31,11 @@ int tempering_hmc_chain_launch(const TemperingHmcChainReq& q, hipStream_t st) {
   a.p_noise = q.p_noise; a.u_accept = q.u_accept; a.u_swap = q.u_swap; a.key = q.key(); a.step0 = q.offset;
   size_t smem = 0;
   plan_params(q.e, q.dim, geo, a.energy, a.param_floats, smem);
-  a.table_offset_floats = (int)(smem / sizeof(float));
-  // the energy table (one float per lane group) and the per-slot accept counters (n_replicas <= 64)
-  smem += (size_t)(kBlock / geo.G) * sizeof(float) + 64 * sizeof(uint32_t);
-  const int lpb = (kBlock / geo.G) / q.n_replicas;
-  const int64_t blocks = ceil_div64(q.n_ladders, lpb);
+  const int64_t blocks = ladder::plan(geo, q.n_replicas, q.n_ladders, smem, a.table_offset_floats);
+  smem += 64 * sizeof(uint32_t);  // behind the energy table: the per-slot accept counters (n_replicas <= 64)
   if (blocks > 0x7fffffffLL) return fail(EBM_EINVAL, "%s: too many ladders for one launch", who);
   const dim3 grid((unsigned)blocks);
-  switch (q.e.kind) {
-    case EBM_ENERGY_DOUBLE_WELL: tempering_hmc::launch_double_well(geo, grid, smem, st, a); break;
-    case EBM_ENERGY_HARMONIC:    tempering_hmc::launch_harmonic(geo, grid, smem, st, a); break;
-    case EBM_ENERGY_GAUSSIAN:    tempering_hmc::launch_gaussian(geo, grid, smem, st, a); break;
-    case EBM_ENERGY_ROSENBROCK:  tempering_hmc::launch_rosenbrock(geo, grid, smem, st, a); break;
-    case EBM_ENERGY_ACKLEY:      tempering_hmc::launch_ackley(geo, grid, smem, st, a); break;
-    case EBM_ENERGY_RASTRIGIN:   tempering_hmc::launch_rastrigin(geo, grid, smem, st, a); break;
-    default:                     tempering_hmc::launch_gmm(geo, grid, smem, st, a); break;
-  }
+  for_kind(q.e.kind, [&](auto K) { tempering_hmc::launch_kind<decltype(K)::value>(geo, grid, smem, st, a); });
   return check_launch(who);
 }
 
