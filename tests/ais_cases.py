@@ -7,6 +7,7 @@ import functools
 import torch
 
 from tempering_cases import energy_spec, model_of, oracle_of  # noqa: F401  (re-exported for the tests)
+from tempering_cases import start_scale
 from tempering_hmc_cases import MARGIN_BAR, STEP_C, leapfrog_steps  # noqa: F401
 
 
@@ -34,11 +35,13 @@ def _hamiltonian(u, p):
     return u.clamp(min=-1e10, max=1e10) + (0.5 * torch.sum(p.square(), dim=-1)).clamp_(min=0.0, max=1e10)
 
 
-def restate(energy, x0, z, u, betas, eps, n_leapfrog, base_std, dtype=torch.float32):
+def restate(energy, x0, z, u, betas, eps, n_leapfrog, base_std, dtype=torch.float32, force_betas=None):
     """x0 [n, dim], z [T, n, dim], u [T, n], betas fp32 [T + 1], eps: T step sizes -> final states [n, dim], logw [n], the accept
     mask [T, n] and the margins |u - a| (inf where the threshold is NaN).  The coefficients the contract forms in fp32 -- the
-    difference of the betas, 1 - beta, inv_var0 -- are formed in fp32 here too and then used in `dtype`."""
+    difference of the betas, 1 - beta, inv_var0 -- are formed in fp32 here too and then used in `dtype`.  force_betas: another table for the force of the trajectory alone -- a
+    deliberately wrong walk (tests/test_tempered_landscape_bars.py); None is the algorithm."""
     T = z.shape[0]
+    fb = betas if force_betas is None else force_betas
     inv_var0 = f32(1.0 / float(base_std) ** 2)
     half_inv = 0.5 * inv_var0
     x = x0.to(dtype).clone()
@@ -50,13 +53,14 @@ def restate(energy, x0, z, u, betas, eps, n_leapfrog, base_std, dtype=torch.floa
         b = float(betas[t])
         db = float(betas[t] - betas[t - 1])
         b0 = float(1.0 - betas[t])
-        c0 = b0 * inv_var0
         e0, e = base(x), energy.energy(x)
         y = db * (e0 - e) - comp  # the compensated (Kahan) pair
         s = logw + y
         comp = torch.where(torch.isfinite(s), (s - logw) - y, torch.zeros_like(s))
         logw = s
-        force = lambda q: (-(c0 * q + b * energy.grad(q))).clamp_(min=-1e6, max=1e6)  # noqa: E731
+        bf = float(fb[t])
+        c0 = float(1.0 - fb[t]) * inv_var0
+        force = lambda q: (-(c0 * q + bf * energy.grad(q))).clamp_(min=-1e6, max=1e6)  # noqa: E731
         eps_t = torch.tensor(f32(eps[t - 1]), dtype=dtype)  # the fp32 table entry (oracle/hmc.py: eps as a tensor of the state's dtype)
         p = z[t - 1].to(dtype)
         h0 = _hamiltonian(b0 * e0 + b * e, p)
@@ -95,13 +99,38 @@ CASES = [
 ]
 
 
+# Rosenbrock and Ackley at the smallest dim of every lane geometry (tempering_cases.LANDSCAPE_CASES; one vector per lane here),
+# with the step sizes of STEP_C_AT below; ackley_c3 is Ackley's product form (c = 3), and one case is a single chain.  Proposals
+# rejected on the CPU restatement, in the order of the list:
+#   rosenbrock 186 of 771, 23 of 222, 13 of 148, 22 of 148, 9 of 148, 13 of 148, 20 of 222; 1 of 12 (one chain)
+#   ackley     279 of 771, 69 of 222, 18 of 148, 40 of 148, 34 of 148, 26 of 148, 74 of 222; 4 of 148 (c = 3)
+_LANDSCAPE_SHAPES = [(2, 257, 3), (5, 37, 6), (12, 37, 4), (32, 37, 4), (64, 37, 4), (100, 37, 4), (256, 37, 6)]
+LANDSCAPE_CASES = ([("rosenbrock",) + s for s in _LANDSCAPE_SHAPES] + [("rosenbrock", 100, 1, 12)]
+                   + [("ackley",) + s for s in _LANDSCAPE_SHAPES] + [("ackley_c3", 12, 37, 4)])
+
+
 def base_std_of(kind):
-    return 0.6 if kind == "rastrigin" else 1.0
+    return start_scale(kind)
+
+
+# The landscapes of LANDSCAPE_CASES: a factor per (kind, dim), chosen on the CPU restatement so that every case rejects between
+# 2 % and 50 % of its proposals (tempering_hmc_cases.STEP_C_AT has the replica-exchange cases' own).
+STEP_C_AT = {
+    ("rosenbrock", 2): 0.28, ("rosenbrock", 5): 0.28, ("rosenbrock", 12): 0.28, ("rosenbrock", 32): 0.4, ("rosenbrock", 64): 0.4,
+    ("rosenbrock", 100): 0.5, ("rosenbrock", 256): 0.6,
+    ("ackley", 2): 0.3, ("ackley", 5): 0.6, ("ackley", 12): 0.6, ("ackley", 32): 1.0, ("ackley", 64): 1.0, ("ackley", 100): 1.0,
+    ("ackley", 256): 1.6,
+}
+
+
+def step_c(kind, dim):
+    kind = "ackley" if kind == "ackley_c3" else kind
+    return STEP_C_AT[(kind, dim)] if (kind, dim) in STEP_C_AT else 2.0 * STEP_C[kind]
 
 
 def step_sizes(kind, dim, T):
     """One step size per transition, each a little shorter than the one before: the kernel has to read the table."""
-    base = 2.0 * STEP_C[kind] * (2.0 / dim) ** 0.25  # (twice the replica-exchange cases': a walk that starts in the base's equilibrium rejects little)
+    base = step_c(kind, dim) * (2.0 / dim) ** 0.25  # (STEP_C: twice the replica-exchange cases': a walk that starts in the base's equilibrium rejects little)
     return tuple(base * (1.0 - 0.02 * t) for t in range(T))
 
 

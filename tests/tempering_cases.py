@@ -29,6 +29,25 @@ class Rastrigin:
         return g.detach()
 
 
+class Landscape:
+    """A landscape energy of the package (Rosenbrock, Ackley): the model's CPU forward with an autograd gradient, in the
+    dtype of the state it is handed -- fp32 the oracle, float64 the referee (the parameters are Python doubles: to64 has
+    nothing to upcast)."""
+
+    def __init__(self, model):
+        self.model = model
+
+    def energy(self, x):
+        return self.model.forward(x)
+
+    def grad(self, x):
+        with torch.enable_grad():
+            leaf = x.detach().clone().requires_grad_(True)
+            e = self.energy(leaf)
+            (g,) = torch.autograd.grad(e, leaf, grad_outputs=torch.ones_like(e))
+        return g.detach()
+
+
 def ladder(sigma, temps):
     """noise_coef[R], beta[R]: formed in double, rounded to fp32 once."""
     t = torch.tensor(list(temps), dtype=torch.float64)
@@ -95,12 +114,20 @@ def energy_spec(kind, dim):
         return {"kind": kind, "means": 1.5 * torch.randn(8, dim, generator=g), "sigma": 1.0}
     if kind == "rastrigin":
         return {"kind": kind, "a": 1.0}
+    if kind == "rosenbrock":  # b = 4: at the default b = 100 ETA below is past the Euler stability limit of the hot slots
+        return {"kind": kind, "a": 1.0, "b": 4.0}
+    if kind == "ackley":
+        return {"kind": kind, "a": 20.0, "b": 0.2, "c": 2.0 * math.pi}
+    if kind == "ackley_c3":  # c != 2 pi: the kernels' product form sincosf(c x)
+        return {"kind": "ackley", "a": 20.0, "b": 0.2, "c": 3.0}
     raise ValueError(kind)
 
 
 def oracle_of(spec):
     from helpers import oracle_energy
 
+    if spec["kind"] in ("rosenbrock", "ackley"):
+        return Landscape(model_of(spec))
     return Rastrigin(spec["a"]) if spec["kind"] == "rastrigin" else oracle_energy(spec)
 
 
@@ -108,7 +135,16 @@ def model_of(spec, device=None):
     import torchebm_amd as ta
     from helpers import package_model
 
+    if spec["kind"] == "rosenbrock":
+        return ta.core.RosenbrockModel(a=spec["a"], b=spec["b"], device=device)
+    if spec["kind"] == "ackley":
+        return ta.core.AckleyModel(a=spec["a"], b=spec["b"], c=spec["c"], device=device)
     return ta.core.RastriginModel(a=spec["a"], device=device) if spec["kind"] == "rastrigin" else package_model(spec, device)
+
+
+def start_scale(kind):
+    """The scale of the normal starts: the rippled and the curved-valley landscapes start nearer their minima."""
+    return 0.6 if kind in ("rastrigin", "rosenbrock") else 1.0
 
 
 # (kind, dim, R, n_ladders, swap_every, k): the smallest shapes that reach every hazard of the kernel --
@@ -141,6 +177,17 @@ YARDSTICK_CASES = [
     ("rastrigin", 32, 4, 257, 3, 12),
     ("rastrigin", 260, 2, 37, 1, 4),
 ]
+# The two landscapes with a structure along the row -- Rosenbrock's neighbour exchange, Ackley's mean over dim -- at the smallest
+# dim of every lane geometry: 2 G = 1, 5 G = 2 masked, 12 G = 4 masked, 32 G = 8 full, 64 G = 16 (the DPP wrap over a whole
+# 16-lane row), 100 G = 32 masked (__shfl), 256 G = 64 full (R = 4: one ladder over four waves), 260 two vectors per lane.
+# R = 3 at dim 100 and R = 5 at dim 32 leave idle lane groups.  ackley_c3 is Ackley's product form (c = 3), and one case is
+# a single ladder.  Swaps accepted on the CPU restatement, in the order of the list:
+#   rosenbrock 1740 of 2313, 133 of 222, 170 of 333, 143 of 296, 76 of 333, 39 of 148, 11 of 222, 17 of 74; 1 of 4 (one ladder)
+#   ackley     1829 of 2313, 182 of 222, 294 of 333, 284 of 296, 314 of 333, 140 of 148, 205 of 222, 66 of 74; 293 of 333 (c = 3)
+_LANDSCAPE_SHAPES = [(2, 4, 257, 1, 6), (5, 3, 37, 1, 6), (12, 4, 37, 1, 6), (32, 5, 37, 3, 12), (64, 4, 37, 1, 6), (100, 3, 37, 1, 4),
+                     (256, 4, 37, 3, 12), (260, 2, 37, 1, 4)]
+LANDSCAPE_CASES = ([("rosenbrock",) + s for s in _LANDSCAPE_SHAPES] + [("rosenbrock", 100, 3, 1, 3, 12)]
+                   + [("ackley",) + s for s in _LANDSCAPE_SHAPES] + [("ackley_c3", 12, 4, 37, 1, 6)])
 ETA, SIGMA = 0.004, 1.0  # (a step size at which the hottest slot of the double well stays stable from these starts)
 
 
@@ -158,7 +205,7 @@ def case(kind, dim, R, n, swap_every, k):
     The seed is the first whose fp64 restatement has no decision closer than MARGIN_BAR to its threshold."""
     spec = energy_spec(kind, dim)
     temps = TEMPS[R]
-    scale = 1.0 if kind != "rastrigin" else 0.6
+    scale = start_scale(kind)
     for seed in range(200):
         x0, noise, u = draw_inputs(seed, n, R, dim, k, swap_every, scale)
         from helpers import to64

@@ -101,14 +101,29 @@ def closest_call(ref):
 STEP_C = {"double_well": 0.12, "harmonic": 0.5, "gaussian": 0.25, "gmm": 0.45, "rastrigin": 0.05}
 
 
+# The landscapes with a neighbour coupling or a mean over the row follow no one law from dim 2 to 256: a factor per (kind, dim),
+# chosen on the CPU restatement so that every case of LANDSCAPE_CASES rejects between 2 % and 50 % of its proposals.
+STEP_C_AT = {
+    ("rosenbrock", 2): 0.2, ("rosenbrock", 5): 0.2, ("rosenbrock", 12): 0.2, ("rosenbrock", 32): 0.3, ("rosenbrock", 64): 0.3,
+    ("rosenbrock", 100): 0.3, ("rosenbrock", 256): 0.45,
+    ("ackley", 2): 0.3, ("ackley", 5): 0.3, ("ackley", 12): 0.6, ("ackley", 32): 1.0, ("ackley", 64): 1.0, ("ackley", 100): 1.0,
+    ("ackley", 256): 1.6,
+}
+
+
+def step_c(kind, dim):
+    kind = "ackley" if kind == "ackley_c3" else kind
+    return STEP_C_AT[(kind, dim)] if (kind, dim) in STEP_C_AT else STEP_C[kind]
+
+
 def step_sizes(kind, dim, R):
     """One step size per slot: the hotter slots step a little shorter, so the kernel has to follow the slot's own value."""
-    base = STEP_C[kind] * (2.0 / dim) ** 0.25
+    base = step_c(kind, dim) * (2.0 / dim) ** 0.25
     return tuple(base * (1.0 - 0.02 * r) for r in range(R))
 
 
 def leapfrog_steps(dim):
-    return {2: 5, 5: 4, 32: 3, 100: 4, 256: 3}.get(dim, 4)
+    return {2: 5, 5: 4, 32: 3, 100: 4, 256: 3}.get(dim, 4)  # (dims 12 and 64 of the landscape cases: 4)
 
 
 # (kind, dim, R, n_ladders, swap_every, n_mh): the smallest shapes that reach every hazard of the kernel -- dim 2 one lane
@@ -132,6 +147,19 @@ CASES = [
 ]
 
 
+# Rosenbrock and Ackley at the smallest dim of every lane geometry (tempering_cases.LANDSCAPE_CASES; one vector per lane here),
+# with the step sizes of STEP_C_AT; ackley_c3 is Ackley's product form (c = 3), and one case is a single ladder.  On the CPU
+# restatement, in the order of the list (proposals rejected; swaps accepted):
+#   rosenbrock 611 of 3084, 97 of 666, 57 of 592, 229 of 1110, 101 of 592, 32 of 444, 305 of 888; 5 of 36 (one ladder)
+#              974 of 1285, 62 of 111, 106 of 222, 80 of 222, 35 of 222, 10 of 148, 6 of 185; 0 of 4
+#   ackley     1300 of 3084, 73 of 666, 119 of 592, 186 of 1110, 69 of 592, 47 of 444, 52 of 888; 29 of 592 (c = 3)
+#              839 of 1285, 58 of 111, 125 of 222, 161 of 222, 133 of 222, 76 of 148, 106 of 185; 126 of 222
+_LANDSCAPE_SHAPES = [(2, 4, 257, 1, 3), (5, 3, 37, 2, 6), (12, 4, 37, 1, 4), (32, 5, 37, 2, 6), (64, 4, 37, 1, 4), (100, 3, 37, 1, 4),
+                     (256, 4, 37, 2, 6)]
+LANDSCAPE_CASES = ([("rosenbrock",) + s for s in _LANDSCAPE_SHAPES] + [("rosenbrock", 100, 3, 1, 3, 12)]
+                   + [("ackley",) + s for s in _LANDSCAPE_SHAPES] + [("ackley_c3", 12, 4, 37, 1, 4)])
+
+
 def draw_inputs(seed, n, R, dim, n_mh, swap_every, scale):
     g = torch.Generator().manual_seed(seed)
     x0 = scale * torch.randn(n, R, dim, generator=g)
@@ -150,7 +178,7 @@ def case(kind, dim, R, n, swap_every, n_mh):
 
     spec = energy_spec(kind, dim)
     temps, eps, L = TEMPS[R], step_sizes(kind, dim, R), leapfrog_steps(dim)
-    scale = 1.0 if kind != "rastrigin" else 0.6
+    scale = tempering_cases.start_scale(kind)
     for seed in range(200):
         x0, z, ua, us = draw_inputs(seed, n, R, dim, n_mh, swap_every, scale)
         ref64 = restate(to64(oracle_of(spec)), x0, z, ua, us, eps, L, temps, swap_every, torch.float64, thin=2)

@@ -184,9 +184,17 @@ def _double_well_log_z(h, b, dim):
     return dim * math.log(torch.trapezoid(torch.exp(-h * (x * x - b) ** 2), x).item())
 
 
+def _rastrigin_log_z(a, dim):
+    x = torch.linspace(-8.0, 8.0, 320001, dtype=torch.float64)
+    return dim * math.log(torch.trapezoid(torch.exp(-(a + x * x - a * torch.cos(2.0 * math.pi * x))), x).item())
+
+
 LAW = {
     "harmonic": (lambda dev: ta.HarmonicModel(k=4.0, device=dev), 8, 1.0, 0.35, 4.0 * math.log(2.0 * math.pi / 4.0)),
     "double_well": (lambda dev: ta.DoubleWellModel(barrier_height=2.0, b=1.0, device=dev), 4, 1.0, 0.15, _double_well_log_z(2.0, 1.0, 4)),
+    # a landscape kind (the lane-group energies of csrc/landscape_energies.h): independent coordinates, so the truth is one
+    # integral.  The CPU eager route alone meets the ess bar at T = 32 (ess 3754 of 4096, z = 0.22)
+    "rastrigin": (lambda dev: ta.core.RastriginModel(a=1.0, device=dev), 4, 0.7, 0.15, _rastrigin_log_z(1.0, 4)),
     "ring": (lambda dev: ta.core.ring_mixture(8, 5, radius=3.0, sigma=0.5, device=dev), 5, 2.5, 0.3, 2.5 * math.log(2.0 * math.pi * 0.25)),
 }
 
