@@ -602,7 +602,10 @@ EBM_API int ebm_mlp_param_grads_f32(const float* acts, int64_t n_rows, int32_t h
 /* Column statistics for the sampler diagnostics (samplers/langevin_dynamics.py:173-185):
  * mean[dim], biased var[dim] clamped to [1e-10, 1e10].  `work` = device double[2*dim + 1], zeroed once by
  * the caller: the kernel's last block finishes the statistics and leaves it zeroed again, so consecutive
- * calls on one stream share it without a memset. */
+ * calls on one stream share it without a memset.  Sums are shifted by row 0 and kept in double; for dim a power of two in
+ * [4, 1024] (and n_chains * dim >= 1024) the shifted values are formed and summed four rows at a time in fp32 first, so the
+ * accuracy of that path is relative to the spread about row 0 -- |d var| <= U var + 14 U mean((x - x[0])^2), U = 2^-24 -- not
+ * to the variance: a first row far from all the others costs it accuracy (tests/chain_stats_cases.py derives the bounds). */
 EBM_API int ebm_chain_stats_f32(const float* x, int64_t n_chains, int32_t dim, float* mean_out,
                         float* var_out, double* work, void* stream);
 
