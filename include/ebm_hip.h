@@ -458,6 +458,56 @@ EBM_API int ebm_ais_mlp_chain_f32(const ebm_energy_t* energy, float* x, float* l
                                   uint8_t* accept_mask, uint32_t* accept_counts, const float* x0, const float* p_noise,
                                   const float* u_accept, uint64_t seed, uint64_t step0, void* stream);
 
+/*
+ * Per-chain running moments: k_steps transitions of a Langevin (sampler = 0) or HMC (sampler = 1) walker per chain that keeps,
+ * beside its state, the time average and the sum of squared deviations of every coordinate -- and of the energy -- over two
+ * halves of the counted steps, in ONE launch (an addition to ABI 9: nothing else moved).  From them the host forms split-R-hat,
+ * a between-sequence effective sample size and burn-in-aware posterior means (torchebm_amd/samplers/moments.py) without a
+ * trajectory: the extra traffic is four state-sized planes per launch, whatever k_steps is.
+ *
+ * Counted states.  The first burn_in transitions are not counted; the remaining 2 h are counted as two halves of h states each.
+ * k_steps - burn_in == 2 h and h >= 2 are required (EBM_EINVAL before any launch).  A counted state is the state AFTER the
+ * transition; for HMC a rejected proposal counts the held state again.
+ *
+ * Accumulator.  Per chain, per coordinate and per half a Welford pair in fp32, every operation rounded on its own; with
+ * c = 1 .. h the count within the half and x the counted value:
+ *     d = x - mean;   mean = mean + d * recip[c - 1];   M2 = M2 + d * (x - mean)
+ * recip: device float[h], recip[c - 1] = (float)(1.0 / c) formed in double and rounded once (a wave-uniform load per step; the
+ * kernel divides nothing).  Both start from zero: c = 1 gives mean = x and M2 = 0 with no special first step.
+ *
+ * Outputs.
+ *   mom     float[4][n_chains][dim]: the planes mean_a, M2_a, mean_b, M2_b (a = first half), written once at the end.
+ *   e_mom   NULL, or float[4][n_chains]: the same four quantities for the energy E(x) of the counted states, the value the
+ *           kind's evaluation returns, unclamped.  HMC: the energy the transition carries (no evaluation).  Langevin: the
+ *           evaluation at the top of the next step returns energy and gradient together, plus one evaluation behind the last
+ *           step; with e_mom == NULL the Langevin kernel is another instantiation that carries no group reduction.
+ *   x       in/out, the final states.
+ *   traj    NULL, or float[n_chains][2 h][dim]: the counted states; e_traj: NULL, or float[n_chains][2 h]: their energies
+ *           (Langevin: written only when e_mom is given).  For tests and small runs.
+ *   accept_mask / accept_count (HMC; ignored for Langevin): NULL, or uint8[k_steps][n_chains] / device uint32[k_steps] the call
+ *           ADDS to, as in ebm_hmc_chain_f32.
+ * Slots of a lane that hold no column never reach memory.
+ *
+ * Langevin transition (eta, sqrt_eta, noise_coef: constants): x' = (x - eta * dE/dx) + noise_coef * (z * sqrt_eta), every
+ * operation rounded on its own, in the reference's order (ebm_langevin_chain_f32 without clamp).  z is the normal field at
+ * Philox step offset + s, element chain * dim + col -- ebm_langevin_chain_f32's coordinates, so for the element-wise energies
+ * the final states equal that entry's bit for bit -- or the injected noise_or_p[k_steps, n_chains, dim].  u is ignored.
+ *
+ * HMC transition (n_leapfrog, eps: constants): ebm_hmc_chain_f32's on the lane-group kernel of the same geometry: identity
+ * mass, n_leapfrog safe-mode leapfrog steps; energy and force carried from the accepted state, the start's from the
+ * pseudo-transition.  Momentum: the normal field at step offset + 2 t, the accept uniform at offset + 2 t + 1, element chain
+ * -- or injected noise_or_p[k_steps, n_chains, dim] and u[k_steps, n_chains], both or neither (EBM_EINVAL).
+ *
+ * Limits: every analytic energy except EBM_ENERGY_MLP (EBM_EKIND); dim <= 256, one vector per lane (EBM_EDIM, in front of any
+ * device access); constant coefficients, no clamp, no tables, identity mass; 64-bit row indices.  A NULL mom or recip is
+ * EBM_EINVAL.
+ */
+EBM_API int ebm_chain_moments_f32(const ebm_energy_t* energy, float* x, int64_t n_chains, int32_t dim, int32_t sampler,
+                                  int32_t k_steps, int32_t burn_in, float eta, float sqrt_eta, float noise_coef,
+                                  int32_t n_leapfrog, float eps, const float* recip, float* mom, float* e_mom, float* traj,
+                                  float* e_traj, uint8_t* accept_mask, uint32_t* accept_count, const float* noise_or_p,
+                                  const float* u, uint64_t seed, uint64_t offset, void* stream);
+
 /* The accept step with the RNG coordinates in DEVICE memory (rng_state = {seed, step}; the uniforms
  * are drawn at step rng_state[1] + step_delta): the graph-capturable form, see
  * ebm_langevin_step_dev_f32.  No injected-uniform form. */

@@ -498,6 +498,33 @@ int ebm_ais_mlp_chain_f32(const ebm_energy_t* energy, float* x, float* logw, int
                         accept_mask, accept_counts, x0, p_noise, u_accept, seed, step0, stream);
 }
 
+int ebm_chain_moments_f32(const ebm_energy_t* energy, float* x, int64_t n_chains, int32_t dim, int32_t sampler, int32_t k_steps,
+                          int32_t burn_in, float eta, float sqrt_eta, float noise_coef, int32_t n_leapfrog, float eps,
+                          const float* recip, float* mom, float* e_mom, float* traj, float* e_traj, uint8_t* accept_mask,
+                          uint32_t* accept_count, const float* noise_or_p, const float* u, uint64_t seed, uint64_t offset,
+                          void* stream) {
+  const char* who = "ebm_chain_moments_f32";
+  if (energy && energy->kind == EBM_ENERGY_MLP)
+    return fail(EBM_EKIND, "%s: the MLP energy has no running-moments kernel (the samplers' eager route takes it)", who);
+  if (int r = check_energy(energy, dim, who)) return r;
+  if (int r = check_state(x, n_chains, dim, who)) return r;
+  if (sampler != 0 && sampler != 1) return fail(EBM_EINVAL, "%s: sampler=%d (0 = Langevin, 1 = HMC)", who, sampler);
+  const bool hmc = sampler == 1;
+  if (k_steps < 0 || burn_in < 0 || burn_in > k_steps || ((k_steps - burn_in) & 1) || (k_steps - burn_in) / 2 < 2)
+    return fail(EBM_EINVAL, "%s: k_steps=%d burn_in=%d (k_steps - burn_in must be 2 h with h >= 2)", who, k_steps, burn_in);
+  if (hmc && n_leapfrog < 1) return fail(EBM_EINVAL, "%s: n_leapfrog=%d", who, n_leapfrog);
+  if (int r = moments_check_geometry(dim)) return r;
+  if (!recip || !mom) return fail(EBM_EINVAL, "%s: recip / mom is NULL", who);
+  if (hmc && (noise_or_p == nullptr) != (u == nullptr)) return fail(EBM_EINVAL, "%s: p_noise and u must be given together", who);
+  if (n_chains == 0) return 0;
+  if (!aligned16(mom) || (traj && !aligned16(traj)) || (noise_or_p && !aligned16(noise_or_p)))
+    return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  const MomentsChainReq q{*energy, x, n_chains, dim, hmc, k_steps, burn_in, eta, sqrt_eta, noise_coef, n_leapfrog, eps, recip, mom,
+                          e_mom, traj, e_traj, hmc ? accept_mask : nullptr, hmc ? accept_count : nullptr, noise_or_p,
+                          hmc ? u : nullptr, seed, offset};
+  return moments_chain_launch(q, (hipStream_t)stream);
+}
+
 int ebm_leapfrog_kick_drift_f32(const float* x, const float* p, const float* force, float* x_new,
                                 float* p_half, int64_t n_chains, int32_t dim, float eps,
                                 int32_t mass_kind, double mass_scalar, const float* mass_diag,

@@ -117,6 +117,31 @@ struct AisChainReq {
   RngKey key() const { return RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)}; }
 };
 
+struct MomentsChainReq {
+  const ebm_energy_t& e;
+  float* x;                // [n_chains, dim], in/out
+  int64_t n_chains;
+  int32_t dim;
+  bool hmc;                // the sampler: false = Langevin, true = HMC
+  int32_t k_steps, burn_in;
+  float eta, sqrt_eta, noise_coef;  // Langevin
+  int32_t n_leapfrog;               // HMC
+  float eps;
+  const float* recip;      // device [half_len()]
+  float* mom;              // [4, n_chains, dim]
+  float* e_mom;            // [4, n_chains] or null
+  float* traj;             // [n_chains, 2 half_len(), dim] or null
+  float* e_traj;           // [n_chains, 2 half_len()] or null
+  uint8_t* accept_mask;
+  uint32_t* accept_count;
+  const float* noise_or_p;
+  const float* u;
+  uint64_t seed, offset;
+
+  RngKey key() const { return RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)}; }
+  int32_t half_len() const { return (k_steps - burn_in) / 2; }
+};
+
 // The fields the row-major Langevin argument structs share (GaussArgs, BigArgs, RowChainArgs, WideArgs).
 template <class Args>
 inline void fill_langevin(Args& a, const LangevinChainReq& q) {
@@ -228,5 +253,12 @@ int ais_check_geometry(int32_t dim);  // 0, or the refusal (dim > 256)
 // ... on the MLP energy (mlp_wide_ais.hip: the same request; 32 chains per wave around the matrix-core evaluation, n_leapfrog + 1 of them per transition)
 int ais_mlp_chain_launch(const AisChainReq&, hipStream_t);
 int ais_mlp_check_shape(int32_t hidden, int32_t dim);  // 0, or the refusal (hidden width not 64 / 128, dim outside 1 .. 128)
+
+
+// ---------------------------------------------------------------------------------
+// Per-chain running moments (moments.hip: a Langevin or an HMC walker per chain with Welford pairs beside the state)
+// ---------------------------------------------------------------------------------
+int moments_chain_launch(const MomentsChainReq&, hipStream_t);
+int moments_check_geometry(int32_t dim);  // 0, or the refusal (dim > 256)
 
 }  // namespace ebm

@@ -210,6 +210,31 @@ class HamiltonianMonteCarlo(BaseSampler):
             x, model_kwargs, n_steps, thin, return_trajectory, return_diagnostics, generator, hip=(route == "step")
         )
 
+    def sample_moments(
+        self,
+        x: Optional[torch.Tensor] = None,
+        dim: Optional[int] = None,
+        n_steps: int = 100,
+        n_samples: int = 1,
+        burn_in: int = 0,
+        energy: bool = True,
+        *,
+        generator: Optional[torch.Generator] = None,
+    ):
+        """Run ``n_steps`` transitions and return ``(x_final, ChainMoments)``: per-chain time averages and sums of squared
+        deviations over the two halves of the transitions behind ``burn_in`` (a rejected proposal counts the held state
+        again) -- split R-hat, effective sample size and pooled posterior moments without a trajectory
+        (``samplers/moments.py``).  ``energy=True`` (the default: the transition carries it) keeps the same for ``E(x)``;
+        ``ChainMoments.acceptance_rate`` holds accepted / proposed per transition.
+
+        ``n_steps - burn_in`` must be even: when it is odd, one more transition is burnt.  At least four counted
+        transitions are needed (``ValueError``).  On the fused route (CUDA fp32, an analytic energy, ``dim <= 256``,
+        constant step size, ``mass is None``, the plain leapfrog integrator) the call is ONE launch of
+        ``ebm_chain_moments_f32``; anything else runs ``sample(n_steps=1)`` per transition around the same recurrence."""
+        from .moments import sample_moments
+
+        return sample_moments(self, True, x, dim, n_steps, n_samples, burn_in, energy, generator)
+
     def _new_outputs(self, n: int, dim: int, n_kept: int, want_traj: bool, want_diag: bool):
         kw = dict(dtype=self.dtype, device=self.device)
         traj = torch.empty((n, n_kept, dim), **kw) if want_traj else None

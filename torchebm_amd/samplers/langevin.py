@@ -251,6 +251,30 @@ class LangevinDynamics(BaseSampler):
             x, model_kwargs, n_steps, thin, return_trajectory, return_diagnostics, generator, hip=(route == "step")
         )
 
+    def sample_moments(
+        self,
+        x: Optional[torch.Tensor] = None,
+        dim: Optional[Union[int, Tuple[int, ...]]] = None,
+        n_steps: int = 100,
+        n_samples: int = 1,
+        burn_in: int = 0,
+        energy: bool = False,
+        *,
+        generator: Optional[torch.Generator] = None,
+    ):
+        """Run ``n_steps`` steps and return ``(x_final, ChainMoments)``: per-chain time averages and sums of squared
+        deviations over the two halves of the steps behind ``burn_in`` -- split R-hat, effective sample size and pooled
+        posterior moments without a trajectory (``samplers/moments.py``).  ``energy=True`` keeps the same for ``E(x)``.
+
+        ``n_steps - burn_in`` must be even: when it is odd, one more step is burnt.  At least four counted steps are needed
+        (``ValueError``).  Schedulers are reset first, as in ``sample()``.  On the fused route (CUDA fp32, an analytic
+        energy, ``dim <= 256``, constant step size and noise scale, no clamp) the call is ONE launch of
+        ``ebm_chain_moments_f32`` and, for the element-wise energies, ``x_final`` is ``sample()``'s for the same generator
+        state bit for bit; anything else runs ``sample(n_steps=1)`` per step around the same recurrence."""
+        from .moments import sample_moments
+
+        return sample_moments(self, False, x, dim, n_steps, n_samples, burn_in, energy, generator)
+
     # ---------------------------------------------------------------------------------
     # shared helpers
     # ---------------------------------------------------------------------------------
