@@ -508,6 +508,43 @@ EBM_API int ebm_chain_moments_f32(const ebm_energy_t* energy, float* x, int64_t 
                                   float* e_traj, uint8_t* accept_mask, uint32_t* accept_count, const float* noise_or_p,
                                   const float* u, uint64_t seed, uint64_t offset, void* stream);
 
+/*
+ * Underdamped (kinetic) Langevin dynamics in the BAOAB splitting (Leimkuhler & Matthews 2013): k_steps transitions of a walker
+ * per chain that carries a velocity beside its position, in ONE launch (an addition to ABI 9: nothing else moved).  Unit mass,
+ * friction gamma > 0, temperature T > 0 (the target is exp(-E / T)), step h > 0.  One gradient evaluation per step, as
+ * Euler-Maruyama; on a quadratic energy the position marginal is exact for every stable h (var(v) = T (1 - h^2 k / 4)).
+ *
+ * Constants.  The entry forms them in double and rounds each once to fp32:
+ *     hh = h / 2;   c1 = exp(-gamma h);   c2 = sqrt(T * (-expm1(-2 gamma h)));   sqrt_temp = sqrt(T)
+ *
+ * Recurrence.  A chain carries x, v and g = dE/dx(x): the raw gradient of the kind's evaluation, no clamp (a NaN propagates
+ * and stays in its chain).  The start's gradient comes from one evaluation in front of the loop.  Step s = 0 .. k_steps - 1,
+ * every operation rounded on its own:
+ *     v = v - hh * g            (B)
+ *     x = x + hh * v            (A)
+ *     v = c1 * v + c2 * z       (O)
+ *     x = x + hh * v            (A)
+ *     g = dE/dx(x)
+ *     v = v - hh * g            (B)
+ * z is the normal field at Philox step offset + 1 + s, element chain * dim + col -- or the injected noise[k_steps, n_chains,
+ * dim].  The closing kick of a step and the opening kick of the next are NOT merged: the bits do not depend on where a run is
+ * cut, so (k1, offset) then (k2, offset + k1) with draw_v0 = 0 equals one call of k1 + k2.
+ *
+ * Start velocity.  draw_v0 != 0: v is output only and the walk starts from sqrt_temp * z0, z0 the normal field at step offset
+ * (also when noise is injected).  draw_v0 == 0: v is read -- velocities that persist across calls.  A call owns the Philox
+ * steps offset .. offset + k_steps either way.
+ *
+ * Outputs.  x and v are updated in place and stored once.  traj: NULL, or float[n_chains][k_steps / thin][dim], the position
+ * after step s whenever (s + 1) % thin == 0.  Slots of a lane that hold no column never reach memory.
+ *
+ * Limits: every analytic energy except EBM_ENERGY_MLP (EBM_EKIND); 1 <= dim <= 256, one vector per lane (EBM_EDIM, in front
+ * of any device access); constants only: no clamp, no tables, no mass matrix, no diagnostics records; 64-bit row indices.
+ * EBM_EINVAL with no buffer touched: a NULL energy, x or v; k_steps < 1; thin < 1; h, gamma or temperature not positive.
+ */
+EBM_API int ebm_kinetic_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim,
+                                  int32_t k_steps, double h, double gamma, double temperature, int32_t draw_v0, int32_t thin,
+                                  float* traj, const float* noise, uint64_t seed, uint64_t offset, void* stream);
+
 /* The accept step with the RNG coordinates in DEVICE memory (rng_state = {seed, step}; the uniforms
  * are drawn at step rng_state[1] + step_delta): the graph-capturable form, see
  * ebm_langevin_step_dev_f32.  No injected-uniform form. */

@@ -25,4 +25,5 @@ from .samplers import (  # noqa: F401
     LangevinDynamics,
     ReplicaExchangeHMC,
     ReplicaExchangeLangevin,
+    UnderdampedLangevin,
 )

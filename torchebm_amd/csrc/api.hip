@@ -525,6 +525,31 @@ int ebm_chain_moments_f32(const ebm_energy_t* energy, float* x, int64_t n_chains
   return moments_chain_launch(q, (hipStream_t)stream);
 }
 
+int ebm_kinetic_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t k_steps,
+                          double h, double gamma, double temperature, int32_t draw_v0, int32_t thin, float* traj,
+                          const float* noise, uint64_t seed, uint64_t offset, void* stream) {
+  const char* who = "ebm_kinetic_chain_f32";
+  if (energy && energy->kind == EBM_ENERGY_MLP)
+    return fail(EBM_EKIND, "%s: the MLP energy has no underdamped-Langevin kernel (the sampler's eager route takes it)", who);
+  if (int r = check_energy(energy, dim, who)) return r;
+  if (int r = check_state(x, n_chains, dim, who)) return r;
+  if (!v) return fail(EBM_EINVAL, "%s: velocity pointer is NULL", who);
+  if (k_steps < 1 || thin < 1) return fail(EBM_EINVAL, "%s: k_steps=%d thin=%d (both must be >= 1)", who, k_steps, thin);
+  if (!(h > 0.0) || !(gamma > 0.0) || !(temperature > 0.0) || !std::isfinite(h) || !std::isfinite(gamma) || !std::isfinite(temperature))
+    return fail(EBM_EINVAL, "%s: h=%g gamma=%g temperature=%g (all must be positive and finite)", who, h, gamma, temperature);
+  if (int r = kinetic_check_geometry(dim)) return r;
+  if (n_chains == 0) return 0;
+  if (!aligned16(v) || (traj && !aligned16(traj)) || (noise && !aligned16(noise)))
+    return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  // the constants of the splitting: formed in double, each rounded once
+  const float hh = (float)(0.5 * h);
+  const float c1 = (float)exp(-gamma * h);
+  const float c2 = (float)sqrt(temperature * (-expm1(-2.0 * gamma * h)));
+  const float sqrt_temp = (float)sqrt(temperature);
+  const KineticChainReq q{*energy, x, v, n_chains, dim, k_steps, hh, c1, c2, sqrt_temp, draw_v0 != 0, thin, traj, noise, seed, offset};
+  return kinetic_chain_launch(q, (hipStream_t)stream);
+}
+
 int ebm_leapfrog_kick_drift_f32(const float* x, const float* p, const float* force, float* x_new,
                                 float* p_half, int64_t n_chains, int32_t dim, float eps,
                                 int32_t mass_kind, double mass_scalar, const float* mass_diag,

@@ -142,6 +142,23 @@ struct MomentsChainReq {
   int32_t half_len() const { return (k_steps - burn_in) / 2; }
 };
 
+struct KineticChainReq {
+  const ebm_energy_t& e;
+  float* x;                // [n_chains, dim], in/out
+  float* v;                // [n_chains, dim]: in/out, output only with draw_v0
+  int64_t n_chains;
+  int32_t dim, k_steps;
+  float hh, c1, c2, sqrt_temp;  // h / 2, exp(-gamma h), sqrt(T (1 - exp(-2 gamma h))), sqrt(T): formed in double, rounded once
+  bool draw_v0;
+  int32_t thin;
+  float* traj;             // [n_chains, n_kept(), dim] or null
+  const float* noise;      // [k_steps, n_chains, dim] or null
+  uint64_t seed, offset;
+
+  RngKey key() const { return RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)}; }
+  int32_t n_kept() const { return k_steps / thin; }
+};
+
 // The fields the row-major Langevin argument structs share (GaussArgs, BigArgs, RowChainArgs, WideArgs).
 template <class Args>
 inline void fill_langevin(Args& a, const LangevinChainReq& q) {
@@ -260,5 +277,11 @@ int ais_mlp_check_shape(int32_t hidden, int32_t dim);  // 0, or the refusal (hid
 // ---------------------------------------------------------------------------------
 int moments_chain_launch(const MomentsChainReq&, hipStream_t);
 int moments_check_geometry(int32_t dim);  // 0, or the refusal (dim > 256)
+
+// ---------------------------------------------------------------------------------
+// Underdamped Langevin, BAOAB (kinetic.hip: a walker per chain with position, velocity and carried gradient in registers)
+// ---------------------------------------------------------------------------------
+int kinetic_chain_launch(const KineticChainReq&, hipStream_t);
+int kinetic_check_geometry(int32_t dim);  // 0, or the refusal (dim > 256)
 
 }  // namespace ebm

@@ -3,9 +3,11 @@
 from .ais import AISResult, AnnealedImportanceSampling
 from .descent import GradientDescentSampler, NesterovSampler
 from .hamiltonian import HamiltonianMonteCarlo
+from .kinetic import UnderdampedLangevin
 from .langevin import LangevinDynamics
 from .moments import ChainMoments, RunningMoments
 from .tempering import ReplicaExchangeHMC, ReplicaExchangeLangevin
 
 __all__ = ["LangevinDynamics", "HamiltonianMonteCarlo", "GradientDescentSampler", "NesterovSampler",
-           "ReplicaExchangeLangevin", "ReplicaExchangeHMC", "AnnealedImportanceSampling", "AISResult", "ChainMoments", "RunningMoments"]
+           "ReplicaExchangeLangevin", "ReplicaExchangeHMC", "AnnealedImportanceSampling", "AISResult", "ChainMoments", "RunningMoments",
+           "UnderdampedLangevin"]

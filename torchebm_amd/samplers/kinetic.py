@@ -1,0 +1,229 @@
+r"""Underdamped (kinetic) Langevin dynamics in the BAOAB splitting: :class:`UnderdampedLangevin`.
+
+A chain carries a velocity ``v`` beside its position ``x`` (unit mass, friction ``gamma``, temperature ``T``: the target is
+``exp(-E / T)``).  One step of size ``h`` (Leimkuhler & Matthews 2013), with ``g = dE/dx(x)`` carried from the step before:
+
+.. math::
+    v \leftarrow v - \tfrac h2 g,\quad x \leftarrow x + \tfrac h2 v,\quad
+    v \leftarrow e^{-\gamma h} v + \sqrt{T (1 - e^{-2 \gamma h})}\,\xi,\quad
+    x \leftarrow x + \tfrac h2 v,\quad g \leftarrow \nabla E(x),\quad v \leftarrow v - \tfrac h2 g
+
+One gradient evaluation per step, as Euler-Maruyama -- but on a quadratic energy the position marginal is exact for every
+stable step size (Euler-Maruyama's variance is off by ``1 / (1 - eta k / 2)``), and ``var(v) = T (1 - h^2 k / 4)``.
+
+Two execution routes, chosen once per ``sample()`` call (``_route``):
+
+``fused``  CUDA fp32 state, no autocast, one of the analytic energies (not the MLP), ``dim <= 256`` and a constant step size:
+           the whole call -- start velocities, steps, Philox draws, thinned trajectory -- is ONE launch of
+           ``ebm_kinetic_chain_f32`` (include/ebm_hip.h states the recurrence exactly; docs/design/kinetic.md the kernel).
+``eager``  everything else (CPU, any other ``BaseModel``, a scheduler on ``step_size``, wider rows): the same recurrence in
+           torch ops around ``model.gradient``, drawing ``randn(n, dim)`` for the start velocities and once per step.
+
+A fused-eligible call never falls back to eager: a missing library or a failing launch raises.
+"""
+
+from __future__ import annotations
+
+import math
+from typing import Dict, Optional, Tuple, Union
+
+import torch
+
+from .. import _lib, _rng
+from ..core.energies import BaseModel, FusedSpec, fused_spec_for
+from ..core.sampler_base import BaseSampler
+from ..core.schedules import BaseScheduler
+from .tempering import _LadderSampler
+
+FUSED_MAX_DIM = 256  # one vector per lane (csrc/kinetic.hip)
+
+
+def baoab_constants(h: float, friction: float, temperature: float, dtype: torch.dtype = torch.float32) -> Tuple[float, float, float, float]:
+    """``(h / 2, exp(-gamma h), sqrt(T (1 - exp(-2 gamma h))), sqrt(T))``: formed in double, each rounded once to ``dtype``
+    (the constants ``ebm_kinetic_chain_f32`` forms from the same three numbers)."""
+    vals = (0.5 * h, math.exp(-friction * h), math.sqrt(temperature * (-math.expm1(-2.0 * friction * h))), math.sqrt(temperature))
+    return tuple(torch.tensor(vals, dtype=torch.float64).to(dtype).tolist())
+
+
+class UnderdampedLangevin(BaseSampler):
+    """Underdamped Langevin dynamics, BAOAB splitting, unadjusted.
+
+    Args:
+        model: energy model to sample from.
+        step_size: step size ``h``, a float or (eager route) a ``BaseScheduler``.
+        friction: friction ``gamma > 0``.
+        temperature: temperature ``T > 0``; the chains sample ``exp(-E / T)``.
+        dtype, device: where the chains live.
+    """
+
+    def __init__(
+        self,
+        model: BaseModel,
+        step_size: Union[float, BaseScheduler] = 1e-2,
+        friction: float = 1.0,
+        temperature: float = 1.0,
+        dtype: torch.dtype = torch.float32,
+        device: Optional[Union[str, torch.device]] = None,
+    ):
+        super().__init__(model=model, dtype=dtype, device=device)
+        self._register_param("step_size", step_size, positive=True)
+        if not (friction > 0 and math.isfinite(friction)):
+            raise ValueError("friction must be positive")
+        if not (temperature > 0 and math.isfinite(temperature)):
+            raise ValueError("temperature must be positive")
+        self.friction = float(friction)
+        self.temperature = float(temperature)
+
+    # ---------------------------------------------------------------------------------
+    # routing: decided here and nowhere else
+    # ---------------------------------------------------------------------------------
+    def _route(self, x: torch.Tensor) -> Tuple[str, Optional[FusedSpec]]:
+        if not x.is_cuda or x.dtype != torch.float32 or x.ndim != 2:
+            return "eager", None
+        if not self.schedulers["step_size"].is_constant():
+            return "eager", None
+        if self.use_mixed_precision and self.autocast_available:
+            return "eager", None
+        spec = fused_spec_for(self.model, x, None)
+        if spec is None or spec.kind == _lib.ENERGY_MLP or x.shape[1] > FUSED_MAX_DIM:
+            return "eager", None
+        return "fused", spec
+
+    # ---------------------------------------------------------------------------------
+    # public API
+    # ---------------------------------------------------------------------------------
+    @torch.no_grad()
+    def sample(
+        self,
+        x: Optional[torch.Tensor] = None,
+        dim: Optional[Union[int, Tuple[int, ...]]] = None,
+        n_steps: int = 100,
+        n_samples: int = 1,
+        thin: int = 1,
+        return_trajectory: bool = False,
+        return_diagnostics: bool = False,
+        reset_schedulers: bool = True,
+        *,
+        velocity: Optional[torch.Tensor] = None,
+        return_velocity: bool = False,
+        generator: Optional[torch.Generator] = None,
+    ):
+        """Run ``n_steps`` BAOAB steps.
+
+        ``velocity``: the start velocities, shaped as ``x`` (as a call with ``return_velocity=True`` returned them: continue
+        that run); ``None`` draws them from ``N(0, T I)``.
+
+        Returns the final positions ``[n, *shape]`` (or, with ``return_trajectory``, the kept positions
+        ``[n, n_steps // thin, *shape]``); with ``return_diagnostics`` a dict follows, holding ``"mean"`` / ``"var"``
+        (``[n_kept, *shape]``, biased variance clamped to [1e-10, 1e10]) and ``"energy"`` (``[n_kept]``) of the kept
+        positions and ``"kinetic_temperature"``, the mean of ``v^2`` over chains and coordinates of the final velocities -- an
+        estimate of ``T (1 - h^2 E'' / 4)``, a cheap check of the step size; with ``return_velocity`` the final velocities
+        come last.  The caller's ``x`` and ``velocity`` are never written.
+
+        Raises:
+            ValueError: ``thin < 1``, ``x`` and ``dim`` both ``None``, or a ``velocity`` whose shape differs from the state's.
+        """
+        if thin < 1:
+            raise ValueError("thin must be >= 1")
+        if reset_schedulers:
+            self.reset_schedulers()
+        x = self._init_state(x, dim, n_samples, generator)
+        if velocity is not None:
+            if tuple(velocity.shape) != tuple(x.shape):
+                raise ValueError(f"velocity must have the state's shape {tuple(x.shape)}, got {tuple(velocity.shape)}")
+            velocity = velocity.to(device=self.device, dtype=self.dtype)
+        route, spec = self._route(x)
+        if route == "fused":
+            state, v, traj, diag = self._sample_fused(x, velocity, spec, n_steps, thin, return_trajectory, return_diagnostics, generator)
+        else:
+            state, v, traj, diag = self._sample_eager(x, velocity, n_steps, thin, return_trajectory, return_diagnostics, generator)
+        out = (traj if return_trajectory else state,)
+        if return_diagnostics:
+            diag["kinetic_temperature"] = v.square().mean() if v.numel() else torch.full((), float("nan"), dtype=v.dtype, device=v.device)
+            out += (diag,)
+        if return_velocity:
+            out += (v,)
+        return out[0] if len(out) == 1 else out
+
+    def _new_diag(self, n_kept: int, x: torch.Tensor) -> Dict[str, torch.Tensor]:
+        shape = tuple(x.shape[1:])
+        return {
+            "mean": torch.empty(n_kept, *shape, dtype=x.dtype, device=x.device),
+            "var": torch.empty(n_kept, *shape, dtype=x.dtype, device=x.device),
+            "energy": torch.empty(n_kept, dtype=x.dtype, device=x.device),
+        }
+
+    # ---------------------------------------------------------------------------------
+    # route: torch ops
+    # ---------------------------------------------------------------------------------
+    def _sample_eager(self, x, v, n_steps, thin, want_traj, want_diag, generator):
+        n, shape = x.shape[0], tuple(x.shape[1:])
+        n_kept = n_steps // thin
+        traj = torch.empty((n, n_kept, *shape), dtype=x.dtype, device=x.device) if want_traj else None
+        diag = self._new_diag(n_kept, x) if want_diag else None
+        if v is None:
+            sqrt_temp = baoab_constants(1.0, self.friction, self.temperature, x.dtype)[3]
+            v = sqrt_temp * torch.randn(x.shape, dtype=x.dtype, device=x.device, generator=generator)
+        keep = 0
+        with self.autocast_context():
+            g = self._model_gradient(x, {})
+            for s in range(n_steps):
+                hh, c1, c2, _ = baoab_constants(self.get_scheduled_value("step_size"), self.friction, self.temperature, x.dtype)
+                xi = torch.randn(x.shape, dtype=x.dtype, device=x.device, generator=generator)
+                # every operation rounded on its own, in the order of the contract (include/ebm_hip.h)
+                v = v - hh * g
+                x = x + hh * v
+                v = c1 * v + c2 * xi
+                x = x + hh * v
+                g = self._model_gradient(x, {})
+                v = v - hh * g
+                self.step_schedulers()
+                if (s + 1) % thin == 0:
+                    if traj is not None:
+                        traj[:, keep] = x
+                    if diag is not None:
+                        if n > 1:
+                            diag["mean"][keep] = x.mean(dim=0)
+                            diag["var"][keep] = x.var(dim=0, unbiased=False).clamp_(min=1e-10, max=1e10)
+                        else:
+                            diag["mean"][keep] = x.squeeze(0)
+                            diag["var"][keep].zero_()
+                        diag["energy"][keep] = self._model_energy(x, {}).mean()
+                    keep += 1
+        if n_steps == 0:  # never the caller's tensors
+            x, v = x.clone(), v.clone()
+        return x, v, traj, diag
+
+    # ---------------------------------------------------------------------------------
+    # route: one launch of ebm_kinetic_chain_f32
+    # ---------------------------------------------------------------------------------
+    def _sample_fused(self, x, v, spec: FusedSpec, n_steps, thin, want_traj, want_diag, generator):
+        n, dim = x.shape
+        n_kept = n_steps // thin
+        state = _lib.dense_f32(x).clone()  # the kernel updates in place; never the caller's tensors
+        draw_v0 = v is None
+        vel = torch.empty_like(state) if draw_v0 else _lib.dense_f32(v).clone()
+        need_kept = (want_traj or want_diag) and n_kept > 0
+        traj = torch.empty(n, n_kept, dim, dtype=torch.float32, device=x.device) if (want_traj or need_kept) else None
+        seed, step0 = _rng.reserve(generator, x.device, n_steps + 1)
+        stream = _lib.stream_handle(x.device)
+        spec_c = spec.to_c()
+        if n > 0 and n_steps > 0:
+            _lib.call(
+                "ebm_kinetic_chain_f32",
+                spec_c, _lib.ptr(state), _lib.ptr(vel), n, dim, n_steps, self.get_scheduled_value("step_size"), self.friction,
+                self.temperature, int(draw_v0), thin, _lib.ptr(traj) if need_kept else None, None, seed, step0, stream,
+            )
+        elif draw_v0:  # no step: the start velocities alone, the same field
+            if n > 0:
+                flat = torch.empty((n * dim + 3) // 4 * 4, dtype=torch.float32, device=x.device)
+                _lib.call("ebm_noise_fill_f32", _lib.ptr(flat), n * dim, _lib.NOISE_NORMAL, seed, step0, stream)
+                vel = baoab_constants(1.0, self.friction, self.temperature)[3] * flat[: n * dim].view(n, dim)
+        self.advance_schedulers(n_steps)
+        diag = None
+        if want_diag:
+            diag = self._new_diag(n_kept, state)
+            if n > 0 and n_kept > 0:
+                # the kept-state statistics of the replica-exchange samplers: ebm_energy_grad_f32 + ebm_chain_stats_f32
+                _LadderSampler._kept_statistics(self, spec_c, traj, diag, stream)
+        return state, vel, (traj if want_traj else None), diag
