@@ -296,6 +296,8 @@ int launch_langevin_chain_lean(const LangevinChainReq& q, const ChainArgs& a, di
   if (q.e.kind == EBM_ENERGY_DOUBLE_WELL && !q.coef_table && !q.clamp && !q.traj && !ab_switch("EBM_NO_LEAN_FOLD")) {
     ChainArgs f = a;
     if (lean_fold_ok(f)) {
+      // ... on plain f32 instructions (langevin_fold.hip, lean_body PLAIN); the packed-f32 form stays the A/B route
+      if (!ab_switch("EBM_NO_LEAN_PLAIN")) return langevin_lean_fold_plain_launch(q, f.fold_eta, C64, grid.x, st);
       hipLaunchKernelGGL((langevin_chain_lean_kernel<kDoubleWellFold, false, false, false, false, C64>), grid, block, 0, st, f);
       return check_launch("ebm_langevin_chain_f32");
     }

@@ -7,12 +7,20 @@
 #include "chain_launch.h"
 
 namespace ebm {
+
+// langevin_fold.hip: the folded DoubleWell loop on plain f32 instructions (lean_body PLAIN), in a unit of its own for its compile
+// flag.  The caller has checked lean_fold_ok (fold_eta = its E) and the grid; c64 = !lean_counters32.
+int langevin_lean_fold_plain_launch(const LangevinChainReq& q, float fold_eta, bool c64, unsigned blocks, hipStream_t st);
+
 namespace {
 
 constexpr int kBlock = 256;  // 4 waves: one per SIMD of a CU
 // The lean kernels' energy-kind value for the folded DoubleWell loop (lean_body FOLD).  Internal: the launcher picks it for
 // DoubleWell calls that meet lean_fold_ok; it is no ebm_energy_t and no caller passes it.
 constexpr int kDoubleWellFold = 16;
+// ... and the same loop on plain f32 instructions (lean_body PLAIN; langevin_fold.hip): what the launcher takes for those calls.
+// Kind 16 stays the A/B route (EBM_NO_LEAN_PLAIN) and the form tests/test_isa_lean_fold.py pins.
+constexpr int kDoubleWellFoldPlain = 17;
 
 typedef float v2f __attribute__((ext_vector_type(2)));
 
@@ -144,9 +152,17 @@ extern __shared__ __attribute__((aligned(16))) float elem_smem[];
 // Hence a lane whose four final values are finite with |x| < 2^60 never entered the window and equals the literal loop bit for
 // bit.  Every other lane runs the literal loop again from its start values (kept in registers) over all k steps -- after the
 // step loop, so the guard costs the loop nothing.
+//
+// PLAIN (KIND == kDoubleWellFoldPlain, langevin_fold.hip: what the launcher takes whenever the fold applies): the folded step with
+// gradient, drift and noise update written one element at a time, compiled with -fno-slp-vectorize so they stay v_mul_f32 /
+// v_sub_f32 / v_add_f32 -- the same IEEE operations in the same order, so the same bits.  88 vector instructions per float4 group
+// and step where the 2-vector form issues 70 (its 16 v_pk_mul_f32 / v_pk_add_f32 and the two the vectoriser packs in Box-Muller
+// as 36 plain ones), and 1.1 - 1.3 % faster: in this loop a packed-f32 instruction takes more issue time than two plain ones
+// (docs/design/langevin_flat.md; going the other way, packing Box-Muller's prep as well, 67 instructions, is 0.8 % slower).
 template <int KIND, bool TABLE, bool CLAMP, bool TRAJ, bool HEUN, bool DIAG, bool CONTRACT, bool C64>
 __device__ __forceinline__ void lean_body(const ChainArgs& a) {
-  constexpr bool FOLD = KIND == kDoubleWellFold;
+  constexpr bool PLAIN = KIND == kDoubleWellFoldPlain;
+  constexpr bool FOLD = KIND == kDoubleWellFold || PLAIN;
   constexpr bool DW = KIND == EBM_ENERGY_DOUBLE_WELL || FOLD;  // the arithmetic of the literal steps
   static_assert(!FOLD || (!TABLE && !CLAMP && !TRAJ && !HEUN && !DIAG && !CONTRACT), "the fold exists for the plain lean call only");
   const int64_t g = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -219,6 +235,17 @@ __device__ __forceinline__ void lean_body(const ChainArgs& a) {
     const F4 x_start = x;
     auto fold_step = [&](int i) {
       const F4 eps = normal4_of(draw(i));
+      if constexpr (PLAIN) {  // the same operations, one element each
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const float xs = x.v[q];
+          const float v = (xs * xs - a.s1) * xs;
+          const float x1 = xs - a.fold_eta * v;
+          const float dw = eps.v[q] * c.sqrt_eta;
+          x.v[q] = x1 + c.noise_coef * dw;
+        }
+        return;
+      }
 #pragma unroll
       for (int q = 0; q < 4; q += 2) {
         const v2f xv = {x.v[q], x.v[q + 1]}, ev = {eps.v[q], eps.v[q + 1]};
