@@ -129,7 +129,9 @@ EBM_API const char* ebm_last_error_string(void);
  *     out = x1 + noise_coef * dw      (noise_coef = (float) sqrt(2*sigma^2), 0 => ODE step, no noise drawn)
  *     out = clamp(out, cmin, cmax)    if clamp_on   (samplers/langevin_dynamics.py:166-167)
  * eps = noise[e] if noise != NULL, else the native RNG field at step `offset`.
- * `out` may alias `x`.  `grad` may be NULL (zero drift).
+ * `out` may alias `x` (the same pointer: every element is read before it is written, by the lane that writes it; a shifted
+ * overlap is not supported).  `grad` may be NULL (zero drift).  Exactly n_elem floats of `out` are written, whether n_elem is
+ * a multiple of 4 (streaming float4 kernel) or not (float4 groups and a scalar tail): both forms give the same values.
  */
 EBM_API int ebm_langevin_step_f32(const float* x, const float* grad, float* out, const float* noise,
                           int64_t n_elem, float eta, float sqrt_eta, float noise_coef,
@@ -154,6 +156,9 @@ EBM_API int ebm_langevin_step_diffusion_f32(const float* x, const float* grad, f
  * (seed, step) in a device buffer that the graph itself advances lets one captured
  * "gradient + update" iteration be replayed k times per sample() call with fresh noise every time
  * (the launch-bound autograd route of BASELINE config 5).  No injected-noise form.
+ * The call equals ebm_langevin_step_f32 with seed = rng_state[0], offset = rng_state[1] (all 64 bits of both): this entry has
+ * no step_delta argument, the stored step IS the step.  The entries that take one (ebm_hmc_accept_dev_f32,
+ * ebm_noise_fill_dev_f32, the ABI 6 entries below) draw at rng_state[1] + step_delta, a 64-bit sum.  rng_state is only read.
  */
 EBM_API int ebm_langevin_step_dev_f32(const float* x, const float* grad, float* out, int64_t n_elem,
                                       float eta, float sqrt_eta, float noise_coef,
@@ -261,7 +266,10 @@ EBM_API int ebm_hmc_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_ch
  * LeapfrogIntegrator.step / .integrate (integrators/leapfrog.py:63-187).
  *   kick_drift:  f = clamp(force) if safe;  p_half = p + (0.5*eps)*f;  x_new = x + eps*p_half [/ max(m,1e-10)]
  *   kick:        f = clamp(force) if safe;  p_new  = p_half + (0.5*eps)*f;  if safe: nan_to_num(x_new, p_new)
- * `x_new` of kick is updated in place (the NaN scrub); outputs may alias inputs.
+ * `x_new` of kick is updated in place (the NaN scrub: an element that needs none is not stored to and keeps its bits);
+ * outputs may alias inputs element for element: x_new == x and p_half == p (kick_drift), p_new == p_half (kick).  `force`
+ * and `mass_diag` are only read and may alias no output.  The diagonal mass is clamped per element, (m < 1e-10) ? 1e-10 : m,
+ * so a NaN entry stays NaN; nan_to_num sends NaN to 0 and +-inf to +-FLT_MAX.
  */
 EBM_API int ebm_leapfrog_kick_drift_f32(const float* x, const float* p, const float* force,
                                 float* x_new, float* p_half, int64_t n_chains, int32_t dim,
@@ -273,7 +281,12 @@ EBM_API int ebm_leapfrog_kick_f32(float* x_new, const float* p_half, const float
 /*
  * Metropolis accept for the per-step HMC path (samplers/hmc.py:277-292):
  *   d = clamp(h0 - h1, -50, 50); a = min(1, exp(d)); acc = u < a; x = acc ? x_prop : x
- * u = u_or_null[c], or the native uniform field at step `offset`.
+ * u = u_or_null[c], or the native uniform field at step `offset`, element c.
+ * The clamp and the minimum propagate NaN: a NaN Hamiltonian (or inf - inf) rejects.  The comparison is strict: an injected
+ * u = 1 rejects at a = 1, u = 0 accepts at the clamped a = e^-50.  Rejected rows of x are not stored to.
+ *   accept_mask  NULL, or uint8[n_chains]: 1 = accepted, every entry written
+ *   accept_count NULL, or uint32[1] that the call ADDS the number of accepted chains to (atomics; zero it first for a count
+ *                of this call alone)
  */
 EBM_API int ebm_hmc_accept_f32(float* x, const float* x_prop, const float* h0, const float* h1,
                        const float* u, uint8_t* accept_mask, uint32_t* accept_count,
@@ -560,7 +573,8 @@ EBM_API int ebm_hmc_accept_dev_f32(float* x, const float* x_prop, const float* h
  * ebm_descent_chain_f32 runs k fused steps for an analytic energy (v starts at zero and is not
  * returned, as in the reference); eta_table = NULL or device float[k]; traj as in the Langevin chain.
  * ebm_descent_step_f32 is one update with an external gradient (v == NULL: plain descent; else v is
- * updated in place); ebm_lookahead_f32 forms the Nesterov look-ahead point.  Outputs may alias x.
+ * updated in place); ebm_lookahead_f32 forms the Nesterov look-ahead point.  `out` may alias `x` (the same pointer) in
+ * both; `grad` and `v` are distinct from `out` and from each other, and `x` is only read when `out` is another buffer.
  */
 EBM_API int ebm_descent_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_chains, int32_t dim,
                                   int32_t k_steps, float eta, const float* eta_table, int32_t nesterov,
