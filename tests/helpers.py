@@ -3,12 +3,65 @@
 import glob
 import os
 
+import pytest
 import torch
 
 import oracle
 import torchebm_amd as ta
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+class CallRecorder:
+    """stands in for the ctypes handle: every entry returns 0 and is recorded with its arguments (``fail_on``: the entry
+    of that name is recorded and then raises, as a failing launch would)"""
+
+    def __init__(self):
+        self.calls = []
+        self.fail_on = None
+
+    def __getattr__(self, name):
+        def entry(*args):
+            self.calls.append((name, args))
+            if name == self.fail_on:
+                raise RuntimeError(f"{name} failed")
+            return 0
+
+        return entry
+
+    def named(self, prefix):
+        return [(name, args) for name, args in self.calls if name.startswith(prefix)]
+
+
+@pytest.fixture
+def fused_cpu(monkeypatch):
+    """``(make, rec, clones)``: ``make(cls=LangevinDynamics, model=None, **kw)`` builds a sampler whose fused route runs on
+    CPU tensors against the recorder ``rec`` (the real ``_lib.call`` runs); ``clones`` collects what ``Tensor.clone``
+    copied.  Import it into the test module that uses it."""
+    from torchebm_amd import _lib, _rng
+
+    rec = CallRecorder()
+    monkeypatch.setattr(_lib, "lib", lambda: rec)
+    monkeypatch.setattr(_lib, "stream_handle", lambda device: None)
+    monkeypatch.setattr(_rng, "reserve", lambda generator, device, n_steps: (7, 11))
+    monkeypatch.setattr(_lib, "call_counts", type(_lib.call_counts)())
+    clones = []
+    real_clone = torch.Tensor.clone
+
+    def spy(self, *a, **kw):
+        clones.append(self.data_ptr())
+        return real_clone(self, *a, **kw)
+
+    monkeypatch.setattr(torch.Tensor, "clone", spy)
+
+    def make(cls=ta.LangevinDynamics, model=None, step_size=0.01, **kw):
+        model = model or ta.DoubleWellModel(barrier_height=2.0, b=1.0)
+        s = cls(model, step_size=step_size, device="cpu", **kw)
+        spec = model.fused_spec()
+        monkeypatch.setattr(s, "_route", lambda x, model_kwargs: ("fused", spec))
+        return s
+
+    return make, rec, clones
 
 
 def golden_names(prefix):

@@ -7,8 +7,8 @@ import ctypes
 import pytest
 import torch
 
-import torchebm_amd as ta
-from torchebm_amd import _lib, _rng
+from helpers import fused_cpu  # noqa: F401  (the fixture)
+from torchebm_amd import _lib
 
 EINVAL = -1
 X = 0x10000  # never dereferenced: every call below returns before a launch
@@ -62,47 +62,6 @@ def test_the_other_checks_are_those_of_the_in_place_entry():
 # ---------------------------------------------------------------------------------------------------------------
 # the sampler's call pattern
 # ---------------------------------------------------------------------------------------------------------------
-class _Recorder:
-    """stands in for the ctypes handle: every entry returns 0 and is recorded with its arguments"""
-
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def entry(*args):
-            self.calls.append((name, args))
-            return 0
-
-        return entry
-
-
-@pytest.fixture
-def fused_cpu(monkeypatch):
-    """a LangevinDynamics whose fused route runs on CPU tensors against the recorder"""
-    rec = _Recorder()
-    monkeypatch.setattr(_lib, "lib", lambda: rec)
-    monkeypatch.setattr(_lib, "stream_handle", lambda device: None)
-    monkeypatch.setattr(_rng, "reserve", lambda generator, device, n_steps: (7, 11))
-    monkeypatch.setattr(_lib, "call_counts", type(_lib.call_counts)())
-    clones = []
-    real_clone = torch.Tensor.clone
-
-    def spy(self, *a, **kw):
-        clones.append(self.data_ptr())
-        return real_clone(self, *a, **kw)
-
-    monkeypatch.setattr(torch.Tensor, "clone", spy)
-
-    def make(model=None, **kw):
-        model = model or ta.DoubleWellModel(barrier_height=2.0, b=1.0)
-        s = ta.LangevinDynamics(model, step_size=0.01, device="cpu", **kw)
-        spec = model.fused_spec()
-        monkeypatch.setattr(s, "_route", lambda x, model_kwargs: ("fused", spec))
-        return s
-
-    return make, rec, clones
-
-
 def _chain_calls(rec):
     return [(name, args) for name, args in rec.calls if name.startswith("ebm_langevin")]
 

@@ -84,7 +84,7 @@ def test_langevin_grid(cuda_device, name):
     x, nz = x0.to(cuda_device), noise.to(cuda_device)
     if _lib.diag_layout(desc, _lib.DIAG_LANGEVIN, n, dim, True, False) is None:
         # no in-kernel records (dense Gaussians above 128 dims, csrc/gauss_big.hip): `thin` steps per launch and the
-        # statistics from the state, as the sampler does (samplers/langevin.py, _fused_with_state_passes)
+        # statistics from the state, as the sampler does (samplers/_chain_host.py, run_with_state_passes)
         diag = _state_pass_diagnostics(desc, x, nz, table, rows, n, dim, k, thin, cuda_device)
     else:
         layout, rec, work = _records(desc, _lib.DIAG_LANGEVIN, n, dim, k // thin, cuda_device)

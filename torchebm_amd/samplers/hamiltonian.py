@@ -27,11 +27,11 @@ from .. import _lib, _rng
 from ..core.energies import BaseModel, FusedSpec, fused_spec_for
 from ..core.integrator_base import BaseSymplecticIntegrator
 from ..core.module import graph_state_key, warn_once
-from .langevin import _record_scratch, _record_scratch_done, _replay_or_step
 from ..core.sampler_base import BaseSampler
 from ..core.schedules import BaseScheduler
 from ..integrators.registry import resolve_integrator
 from ..integrators.symplectic import LeapfrogIntegrator, _mass_args
+from ._chain_host import new_outputs, record_kept, run_with_records, run_with_state_passes, sample_graph, schedule_table, use_graph
 
 
 class HamiltonianMonteCarlo(BaseSampler):
@@ -235,29 +235,16 @@ class HamiltonianMonteCarlo(BaseSampler):
 
         return sample_moments(self, True, x, dim, n_steps, n_samples, burn_in, energy, generator)
 
-    def _new_outputs(self, n: int, dim: int, n_kept: int, want_traj: bool, want_diag: bool):
-        kw = dict(dtype=self.dtype, device=self.device)
-        traj = torch.empty((n, n_kept, dim), **kw) if want_traj else None
-        diag = None
-        if want_diag:
-            diag = {
-                "mean": torch.empty(n_kept, dim, **kw),
-                "var": torch.empty(n_kept, dim, **kw),
-                "energy": torch.empty(n_kept, **kw),
-                "acceptance_rate": torch.empty(n_kept, **kw),
-            }
-        return traj, diag
-
     # ---------------------------------------------------------------------------------
     # route: per-transition loop
     # ---------------------------------------------------------------------------------
     def _sample_stepwise(self, x, model_kwargs, n_steps, thin, want_traj, want_diag, generator, hip: bool):
         n, dim = x.shape[0], x.shape[1]
-        n_kept = n_steps // thin
-        traj, diag = self._new_outputs(n, dim, n_kept, want_traj, want_diag)
+        traj, diag = new_outputs(self, (n, dim), n_steps // thin, want_traj, want_diag, acceptance=True)
         drift = lambda x_, t_: -self._model_gradient(x_, model_kwargs)  # noqa: E731
+        energy = lambda x_: self._model_energy(x_, model_kwargs).clamp_(min=-1e10, max=1e10)  # noqa: E731
         if hip and n > 0 and self._use_graph(model_kwargs, n_steps):
-            return self._sample_graph(x, n_steps, thin, traj, diag, want_traj, want_diag, generator)
+            return sample_graph(self, x, n_steps, thin, traj, diag, generator, 2, energy)
         if hip:
             x = _lib.dense_f32(x)
             seed, step0 = _rng.reserve(generator, x.device, 2 * n_steps)
@@ -310,17 +297,7 @@ class HamiltonianMonteCarlo(BaseSampler):
                     x = torch.where(accepted.view(-1, *([1] * (x.ndim - 1))), x_prop, x)
 
                 if (i + 1) % thin == 0:
-                    if traj is not None:
-                        traj[:, keep, :] = x
-                    if diag is not None:
-                        diag["mean"][keep] = x.mean(dim=0)
-                        diag["var"][keep] = (
-                            x.var(dim=0, unbiased=False).clamp_(min=1e-10, max=1e10)
-                            if n > 1
-                            else torch.zeros(dim, dtype=self.dtype, device=self.device)
-                        )
-                        diag["energy"][keep] = self._model_energy(x, model_kwargs).clamp_(min=-1e10, max=1e10).mean()
-                        diag["acceptance_rate"][keep] = accepted.float().mean()
+                    record_kept(x, keep, traj, diag, energy, accepted)
                     keep += 1
                 self.step_schedulers()
         out = traj if want_traj else x
@@ -352,10 +329,7 @@ class HamiltonianMonteCarlo(BaseSampler):
     def _graph_eligible(self, model_kwargs: Dict[str, Any]) -> bool:
         return not model_kwargs and not self.use_mixed_precision and self.schedulers["step_size"].is_constant()
 
-    def _use_graph(self, model_kwargs: Dict[str, Any], n_steps: int) -> bool:
-        if self.capture_graph is False or not self._graph_eligible(model_kwargs):
-            return False
-        return self.capture_graph is True or n_steps >= self.GRAPH_MIN_STEPS
+    _use_graph = use_graph
 
     def _graph_for(self, x: torch.Tensor):
         eps = self.get_scheduled_value("step_size")
@@ -397,54 +371,16 @@ class HamiltonianMonteCarlo(BaseSampler):
         self._step_graph = {"key": key, "graph": None, "state": state, "rng": rng, "mask": mask, "body": body}
         return self._step_graph
 
-    def _sample_graph(self, x, n_steps, thin, traj, diag, want_traj, want_diag, generator):
-        x = _lib.dense_f32(x)
-        n, dim = x.shape[0], x.shape[1]
-        g = self._graph_for(x)
-        seed, step0 = _rng.reserve(generator, x.device, 2 * n_steps)
-        as_i64 = lambda v: v - (1 << 64) if v >= (1 << 63) else v  # noqa: E731  (bit pattern of a uint64)
-        g["state"].copy_(x)
-        g["rng"].copy_(torch.tensor([as_i64(seed), as_i64(step0)], dtype=torch.int64), non_blocking=True)
-        state, keep = g["state"], 0
-        for i in range(n_steps):
-            _replay_or_step(self, g, first=(i == 0), more=(i + 1 < n_steps))
-            if (i + 1) % thin == 0:
-                if traj is not None:
-                    traj[:, keep, :] = state
-                if diag is not None:
-                    diag["mean"][keep] = state.mean(dim=0)
-                    diag["var"][keep] = (
-                        state.var(dim=0, unbiased=False).clamp_(min=1e-10, max=1e10)
-                        if n > 1
-                        else torch.zeros(dim, dtype=self.dtype, device=self.device)
-                    )
-                    diag["energy"][keep] = self._model_energy(state, {}).clamp_(min=-1e10, max=1e10).mean()
-                    diag["acceptance_rate"][keep] = g["mask"].float().mean()
-                keep += 1
-        self.advance_schedulers(n_steps)
-        out = traj if want_traj else state.clone()
-        return (out, diag) if want_diag else out
-
     # ---------------------------------------------------------------------------------
     # route: fused HIP kernel
     # ---------------------------------------------------------------------------------
-    def _eps_table(self, eps_vals, device) -> Optional[torch.Tensor]:
-        if len(eps_vals) == 1:
-            return None
-        key = (device, tuple(eps_vals))
-        cached = getattr(self, "_table_cache", None)
-        if cached is None or cached[0] != key:
-            cached = (key, torch.tensor(eps_vals, dtype=torch.float32).to(device, non_blocking=True))
-            self._table_cache = cached
-        return cached[1]
-
     def _launch_hmc(self, spec_c, state, n, dim, eps_vals, t0, n_mh, thin, traj, counts, seed, step, stream, records=None):
         kind, m_scalar, m_diag = _mass_args(self.mass, state)
         if len(eps_vals) == 1:
             eps, table = eps_vals[0], None
         else:
             eps = eps_vals[t0]
-            table = self._eps_table(eps_vals, state.device)[t0 : t0 + n_mh]
+            table = schedule_table(self, eps_vals, state.device)[t0 : t0 + n_mh]
         cptr = None if counts is None else counts.data_ptr() + 4 * t0
         if self.exact:  # the literal body (no in-kernel records: `_sample_fused` asks for none)
             assert records is None
@@ -472,7 +408,7 @@ class HamiltonianMonteCarlo(BaseSampler):
         state = _lib.dense_f32(x)
         if state.data_ptr() == x.data_ptr() and not self.donate_input:
             state = state.clone()  # the kernel updates in place; never touch the caller's tensor unless it was donated
-        traj, diag = self._new_outputs(n, dim, n_kept, want_traj, want_diag)
+        traj, diag = new_outputs(self, (n, dim), n_kept, want_traj, want_diag, acceptance=True)
         sched = self.schedulers["step_size"]
         eps_vals = [sched.get_value()] if sched.is_constant() else sched.preview(n_steps)
         seed, step0 = _rng.reserve(generator, x.device, 2 * n_steps)
@@ -480,73 +416,37 @@ class HamiltonianMonteCarlo(BaseSampler):
         spec_c = spec.to_c()
 
         if n_steps > 0 and n > 0:
-            layout = _lib.diag_layout(spec_c, _lib.DIAG_HMC, n, dim, False, want_traj) if (want_diag and n_kept > 0 and not self.exact) else None
             if not want_diag or n_kept == 0:
                 self._launch_hmc(spec_c, state, n, dim, eps_vals, 0, n_steps, thin, traj, None, seed, step0, stream)
-            elif layout is not None:
-                self._fused_with_records(spec_c, state, n, dim, eps_vals, n_steps, thin, traj, diag, layout, seed, step0, stream)
             else:
-                self._fused_with_state_passes(spec_c, state, n, dim, eps_vals, n_steps, thin, traj, diag, seed, step0, stream)
+                layout = None if self.exact else _lib.diag_layout(spec_c, _lib.DIAG_HMC, n, dim, False, want_traj)
+                self._fused_with_diagnostics(spec_c, state, eps_vals, n_steps, thin, traj, diag, layout, seed, step0, stream)
         self.advance_schedulers(n_steps)
         out = traj if want_traj else state
         return (out, diag) if want_diag else out
 
-    def _fused_with_records(self, spec_c, state, n, dim, eps_vals, n_steps, thin, traj, diag, layout, seed, step0, stream):
-        """Diagnostics from inside the transition kernel (include/ebm_hip.h: ``diag_partials``): at every kept
-        transition each workgroup stores one record (column sums / M2, the energy of the states its chains hold,
-        its accept count); ``ebm_diag_finish_f32`` merges them.  One chain launch + one merge launch per call."""
-        n_blocks, slots, block_elems = layout
-        n_kept = n_steps // thin
-        rec_floats = n_blocks * (2 * slots + 8)
-        chunk = max(1, min(n_kept, self.DIAG_RECORD_BYTES // (4 * rec_floats)))
-        records, work = _record_scratch(self, state.device, stream, chunk * rec_floats, chunk * (3 * dim + 3))
-        done_keep, done = 0, 0
-        while done_keep < n_kept:
-            kk = min(chunk, n_kept - done_keep)
-            n_mh = kk * thin
-            if done_keep + kk == n_kept:
-                n_mh = n_steps - done  # trailing n_steps % thin transitions ride along
-            whole = traj is not None and kk == n_kept
-            piece = traj if (traj is None or whole) else torch.empty(n, kk, dim, dtype=torch.float32, device=state.device)
-            self._launch_hmc(spec_c, state, n, dim, eps_vals, done, n_mh, thin, piece, None, seed, step0 + 2 * done, stream,
-                             records=records)
-            if traj is not None and not whole:
-                traj[:, done_keep : done_keep + kk] = piece
-            sl = slice(done_keep, done_keep + kk)
-            _lib.call(
-                "ebm_diag_finish_f32", _lib.ptr(records), kk, n_blocks, slots, block_elems, n, dim,
-                _lib.ptr(diag["mean"][sl]), _lib.ptr(diag["var"][sl]), _lib.ptr(diag["energy"][sl]),
-                _lib.ptr(diag["acceptance_rate"][sl]), _lib.ptr(work), stream,
-            )
-            done_keep += kk
-            done += n_mh
-        _record_scratch_done(self)
+    def _fused_with_diagnostics(self, spec_c, state, eps_vals, n_steps, thin, traj, diag, layout, seed, step0, stream):
+        """With a ``layout``, diagnostics from inside the transition kernel: at every kept transition each workgroup stores
+        one record (column sums / M2, the energy of the states its chains hold, its accept count) and
+        ``ebm_diag_finish_f32`` merges them (``_chain_host.run_with_records``).  Without one (the MLP energy's
+        matrix-layout kernel, ``exact``): one launch per ``thin`` transitions, each leaving its accepted proposals per
+        transition in ``counts`` (uint32 bit patterns; the trailing launch counts nothing), then the column-statistics
+        and energy kernels on the state (``_chain_host.run_with_state_passes``)."""
+        n, dim = state.shape
+        counts = None if layout is not None else torch.zeros(n_steps, dtype=torch.int32, device=state.device)
+        kept_end = n_steps // thin * thin
 
-    def _fused_with_state_passes(self, spec_c, state, n, dim, eps_vals, n_steps, thin, traj, diag, seed, step0, stream):
-        """Diagnostics for energies without in-kernel records (the MLP energy's matrix-layout kernel): one launch
-        per ``thin`` transitions, then the column-statistics and energy kernels on the state."""
-        n_kept = n_steps // thin
-        counts = torch.zeros(n_steps, dtype=torch.int32, device=state.device)  # uint32 bit pattern
-        work = torch.zeros(2 * dim + 1, dtype=torch.float64, device=state.device)  # the kernel leaves it zeroed
+        def launch(t0, n_mh, piece, records, first):
+            self._launch_hmc(spec_c, state, n, dim, eps_vals, t0, n_mh, thin, piece, counts if t0 < kept_end else None,
+                             seed, step0 + 2 * t0, stream, records=records)
+
+        if layout is not None:
+            run_with_records(self, state, n_steps, thin, traj, diag, layout, stream, launch)
+            return
         energy = torch.empty(n, dtype=torch.float32, device=state.device)
-        done = 0
-        for keep in range(n_kept):
-            self._launch_hmc(spec_c, state, n, dim, eps_vals, done, thin, thin, None, counts, seed, step0 + 2 * done, stream)
-            done += thin
-            if traj is not None:
-                traj[:, keep, :] = state
-            if n > 1:
-                _lib.call(
-                    "ebm_chain_stats_f32",
-                    _lib.ptr(state), n, dim, _lib.ptr(diag["mean"][keep]), _lib.ptr(diag["var"][keep]),
-                    _lib.ptr(work), stream,
-                )
-            else:
-                diag["mean"][keep] = state[0]
-                diag["var"][keep].zero_()
+
+        def mean_energy():
             _lib.call("ebm_energy_grad_f32", spec_c, _lib.ptr(state), n, dim, _lib.ptr(energy), None, stream)
-            diag["energy"][keep] = energy.clamp_(min=-1e10, max=1e10).mean()
-            diag["acceptance_rate"][keep] = counts[done - 1].to(torch.float32) / n
-        if done < n_steps:
-            self._launch_hmc(spec_c, state, n, dim, eps_vals, done, n_steps - done, thin, None, None, seed,
-                             step0 + 2 * done, stream)
+            return energy.clamp_(min=-1e10, max=1e10).mean()
+
+        run_with_state_passes(state, n_steps, thin, traj, diag, stream, launch, mean_energy, counts)

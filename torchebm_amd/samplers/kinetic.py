@@ -25,7 +25,7 @@ A fused-eligible call never falls back to eager: a missing library or a failing 
 from __future__ import annotations
 
 import math
-from typing import Dict, Optional, Tuple, Union
+from typing import Optional, Tuple, Union
 
 import torch
 
@@ -33,7 +33,7 @@ from .. import _lib, _rng
 from ..core.energies import BaseModel, FusedSpec, fused_spec_for
 from ..core.sampler_base import BaseSampler
 from ..core.schedules import BaseScheduler
-from .tempering import _LadderSampler
+from ._chain_host import kept_statistics, new_outputs, record_kept
 
 FUSED_MAX_DIM = 256  # one vector per lane (csrc/kinetic.hip)
 
@@ -145,22 +145,12 @@ class UnderdampedLangevin(BaseSampler):
             out += (v,)
         return out[0] if len(out) == 1 else out
 
-    def _new_diag(self, n_kept: int, x: torch.Tensor) -> Dict[str, torch.Tensor]:
-        shape = tuple(x.shape[1:])
-        return {
-            "mean": torch.empty(n_kept, *shape, dtype=x.dtype, device=x.device),
-            "var": torch.empty(n_kept, *shape, dtype=x.dtype, device=x.device),
-            "energy": torch.empty(n_kept, dtype=x.dtype, device=x.device),
-        }
-
     # ---------------------------------------------------------------------------------
     # route: torch ops
     # ---------------------------------------------------------------------------------
     def _sample_eager(self, x, v, n_steps, thin, want_traj, want_diag, generator):
-        n, shape = x.shape[0], tuple(x.shape[1:])
-        n_kept = n_steps // thin
-        traj = torch.empty((n, n_kept, *shape), dtype=x.dtype, device=x.device) if want_traj else None
-        diag = self._new_diag(n_kept, x) if want_diag else None
+        traj, diag = new_outputs(x, x.shape, n_steps // thin, want_traj, want_diag)
+        energy = lambda x_: self._model_energy(x_, {})  # noqa: E731
         if v is None:
             sqrt_temp = baoab_constants(1.0, self.friction, self.temperature, x.dtype)[3]
             v = sqrt_temp * torch.randn(x.shape, dtype=x.dtype, device=x.device, generator=generator)
@@ -179,16 +169,7 @@ class UnderdampedLangevin(BaseSampler):
                 v = v - hh * g
                 self.step_schedulers()
                 if (s + 1) % thin == 0:
-                    if traj is not None:
-                        traj[:, keep] = x
-                    if diag is not None:
-                        if n > 1:
-                            diag["mean"][keep] = x.mean(dim=0)
-                            diag["var"][keep] = x.var(dim=0, unbiased=False).clamp_(min=1e-10, max=1e10)
-                        else:
-                            diag["mean"][keep] = x.squeeze(0)
-                            diag["var"][keep].zero_()
-                        diag["energy"][keep] = self._model_energy(x, {}).mean()
+                    record_kept(x, keep, traj, diag, energy)
                     keep += 1
         if n_steps == 0:  # never the caller's tensors
             x, v = x.clone(), v.clone()
@@ -222,8 +203,7 @@ class UnderdampedLangevin(BaseSampler):
         self.advance_schedulers(n_steps)
         diag = None
         if want_diag:
-            diag = self._new_diag(n_kept, state)
+            diag = new_outputs(state, state.shape, n_kept, False, True)[1]
             if n > 0 and n_kept > 0:
-                # the kept-state statistics of the replica-exchange samplers: ebm_energy_grad_f32 + ebm_chain_stats_f32
-                _LadderSampler._kept_statistics(self, spec_c, traj, diag, stream)
+                kept_statistics(spec_c, traj, diag, stream)
         return state, vel, (traj if want_traj else None), diag

@@ -27,11 +27,13 @@ import torch
 from .. import _lib, _rng
 from ..core.energies import BaseModel, FusedSpec, fused_spec_for
 from ..core.integrator_base import BaseSDERungeKuttaIntegrator
-from ..core.module import ForwardProbe, graph_blind_spots, graph_state_key, warn_once
+from ..core.module import graph_state_key, warn_once
 from ..core.sampler_base import BaseSampler
 from ..core.schedules import BaseScheduler
 from ..integrators.em import EulerMaruyamaIntegrator, HeunIntegrator
 from ..integrators.registry import resolve_integrator
+from ._chain_host import _CAPTURE_LOCK  # noqa: F401  (the one capture lock: utils.graphed_step takes it from here)
+from ._chain_host import new_outputs, record_kept, run_with_records, run_with_state_passes, sample_graph, schedule_table, use_graph
 
 
 def em_coefficients(eta: float, sigma: float) -> Tuple[float, float, float]:
@@ -41,34 +43,7 @@ def em_coefficients(eta: float, sigma: float) -> Tuple[float, float, float]:
     return eta, eta**0.5, (2.0 * sigma**2) ** 0.5
 
 
-_RECORD_SCRATCH_KEEP_BYTES = 16 << 20
 WIDE_GAUSSIAN_STEP_ROUTE_MIN_CHAINS = 16384  # below: k x (GEMM + update) launches lose to the one fused launch
-_CAPTURE_LOCK = __import__("threading").Lock()  # serialises graph capture: it toggles the process-wide cyclic GC
-
-
-def _record_scratch(sampler, device: torch.device, stream: int, rec_floats: int, work_doubles: int):
-    """The record buffer and the merge's fp64 work row of a diagnostics call, kept on the sampler between calls of the same
-    size on the same stream: the merge leaves the work row zeroed (include/ebm_hip.h), so nothing has to be allocated or
-    filled per call -- on a 0.6 ms sampler call the two allocations and the fill kernel were a tenth of the records' cost.
-    Keyed by the stream: calls on different streams do not share (the zeroed-after-merge contract is per stream order).
-    Only SMALL buffers are kept (<= 16 MiB: the sub-millisecond calls this was built for); a large run's records (up to
-    1 GiB) are per-call temporaries that go back to the caching allocator, as they did before."""
-    if rec_floats * 4 > _RECORD_SCRATCH_KEEP_BYTES:
-        sampler.__dict__.pop("_record_scratch_held", None)
-        return (torch.empty(rec_floats, dtype=torch.float32, device=device),
-                torch.zeros(work_doubles, dtype=torch.float64, device=device))
-    key = (device, stream, rec_floats, work_doubles)
-    held = sampler.__dict__.get("_record_scratch_held")
-    if held is None or held[0] != key or sampler.__dict__.get("_record_scratch_open", False):
-        # (open: the previous call did not reach its last merge -- an exception in between -- so the work row may not be zero)
-        held = (key, torch.empty(rec_floats, dtype=torch.float32, device=device), torch.zeros(work_doubles, dtype=torch.float64, device=device))
-        sampler.__dict__["_record_scratch_held"] = held
-    sampler.__dict__["_record_scratch_open"] = True   # closed by the caller after its last merge (_record_scratch_done)
-    return held[1], held[2]
-
-
-def _record_scratch_done(sampler) -> None:
-    sampler.__dict__["_record_scratch_open"] = False
 
 
 def _gaussian_chain_on_matrix_cores(dim: int) -> bool:
@@ -76,61 +51,6 @@ def _gaussian_chain_on_matrix_cores(dim: int) -> bool:
     packed rows below 20 included; csrc/gauss_shift.hip, gauss_res_shift.hip: widths off multiples of 4 up to 254 on shifted rows;
     csrc/gauss_big.hip: multiples of 4 up to 512)."""
     return dim <= 254 or (dim % 4 == 0 and dim <= 512)
-
-
-def _replay_or_step(sampler, g, first: bool, more: bool) -> None:
-    """One iteration of the graph route: a replay once the graph exists; until then the step body runs eagerly (a real
-    step), and behind the FIRST one of a call the graph is captured -- unless, by default, that step showed side effects
-    (``ForwardProbe``) or the model has attributes the cache key cannot see into.  Shared by the Langevin and HMC samplers
-    (``sampler.capture_graph``, ``sampler._graph_refused``)."""
-    if g["graph"] is not None:
-        g["graph"].replay()
-        return
-    refused = getattr(sampler, "_graph_refused", None)
-    if refused is None:
-        refused = sampler._graph_refused = {}
-    prior = refused.get(g["key"])  # ("probe" | "failed", reasons): a default-mode refusal does not bind capture_graph = True
-    decide = first and more and (prior is None or (sampler.capture_graph is True and prior[0] == "probe"))
-    probe = ForwardProbe(sampler.model, g["state"].device) if decide and sampler.capture_graph is not True else None
-    g["body"]()
-    if not decide:
-        return
-    why = []
-    if probe is not None:
-        why = probe.side_effects()
-        blind = graph_blind_spots(sampler.model)
-        if blind:
-            why.append("attributes the cache key cannot see into: " + ", ".join(blind[:4]))
-    if not why:
-        # The cyclic collector must not run inside the capture: finalising a dead sampler's CUDAGraph (or any tensor whose
-        # storage goes back to the driver) while this stream records aborts the process.  torch.cuda.graph() collects
-        # once on entry; what becomes garbage during the body waits until the capture has ended.
-        # The GC switch is process-wide: the lock keeps a second sampler capturing on another thread from re-enabling it in
-        # the middle of this capture (and the prior state is read inside the lock).
-        import gc
-
-        with _CAPTURE_LOCK:
-            gc_was_on = gc.isenabled()
-            try:
-                graph = torch.cuda.CUDAGraph()
-                gc.disable()
-                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                    g["body"]()
-                g["graph"] = graph
-                return
-            except RuntimeError as exc:  # the forward cannot be captured (host sync, data-dependent control flow ...)
-                if "ebm_" in str(exc):
-                    raise
-                warn_once("capture-graph-failed", f"torchebm_amd: HIP-graph capture of the step route failed ({exc}); "
-                          "continuing with eager launches.", UserWarning)
-                probe, why = None, [f"capture failed: {exc}"]
-            finally:
-                if gc_was_on:
-                    gc.enable()
-    refused.pop(g["key"], None)
-    if len(refused) >= 8:
-        refused.pop(next(iter(refused)))
-    refused[g["key"]] = ("failed" if probe is None else "probe", why)
 
 
 class LangevinDynamics(BaseSampler):
@@ -278,18 +198,6 @@ class LangevinDynamics(BaseSampler):
     # ---------------------------------------------------------------------------------
     # shared helpers
     # ---------------------------------------------------------------------------------
-    def _new_outputs(self, x: torch.Tensor, n_kept: int, want_traj: bool, want_diag: bool):
-        n, shape = x.shape[0], tuple(x.shape[1:])
-        traj = torch.empty((n, n_kept, *shape), dtype=self.dtype, device=self.device) if want_traj else None
-        diag = None
-        if want_diag:
-            diag = {
-                "mean": torch.empty(n_kept, *shape, dtype=self.dtype, device=self.device),
-                "var": torch.empty(n_kept, *shape, dtype=self.dtype, device=self.device),
-                "energy": torch.empty(n_kept, dtype=self.dtype, device=self.device),
-            }
-        return traj, diag
-
     def _clamp_args(self) -> Tuple[int, float, float]:
         if self.clamp is None:
             return 0, 0.0, 0.0
@@ -299,12 +207,11 @@ class LangevinDynamics(BaseSampler):
     # route: per-step loop (eager torch ops, or the per-step HIP kernel)
     # ---------------------------------------------------------------------------------
     def _sample_stepwise(self, x, model_kwargs, n_steps, thin, want_traj, want_diag, generator, hip: bool):
-        n = x.shape[0]
-        n_kept = n_steps // thin
-        traj, diag = self._new_outputs(x, n_kept, want_traj, want_diag)
+        traj, diag = new_outputs(self, x.shape, n_steps // thin, want_traj, want_diag)
+        energy = lambda x_: self._model_energy(x_, model_kwargs)  # noqa: E731
         keep = 0
         if hip and self._use_graph(model_kwargs, n_steps):
-            return self._sample_graph(x, n_steps, thin, traj, diag, want_traj, want_diag, generator)
+            return sample_graph(self, x, n_steps, thin, traj, diag, generator, 1, energy)
         if hip:
             x = _lib.dense_f32(x)
             seed, step0 = _rng.reserve(generator, x.device, n_steps)
@@ -335,16 +242,7 @@ class LangevinDynamics(BaseSampler):
                 self.step_schedulers()
 
                 if (i + 1) % thin == 0:
-                    if traj is not None:
-                        traj[:, keep] = x
-                    if diag is not None:
-                        if n > 1:
-                            diag["mean"][keep] = x.mean(dim=0)
-                            diag["var"][keep] = x.var(dim=0, unbiased=False).clamp_(min=1e-10, max=1e10)
-                        else:
-                            diag["mean"][keep] = x.squeeze(0)
-                            diag["var"][keep].zero_()
-                        diag["energy"][keep] = self._model_energy(x, model_kwargs).mean()
+                    record_kept(x, keep, traj, diag, energy)
                     keep += 1
         out = traj if want_traj else x
         return (out, diag) if want_diag else out
@@ -380,10 +278,7 @@ class LangevinDynamics(BaseSampler):
     capture_graph: Optional[bool] = None
     GRAPH_MIN_STEPS = 8
 
-    def _use_graph(self, model_kwargs: Dict[str, Any], n_steps: int) -> bool:
-        if self.capture_graph is False or not self._graph_eligible(model_kwargs):
-            return False
-        return self.capture_graph is True or n_steps >= self.GRAPH_MIN_STEPS
+    _use_graph = use_graph
 
     def _graph_eligible(self, model_kwargs: Dict[str, Any]) -> bool:
         return (
@@ -395,7 +290,7 @@ class LangevinDynamics(BaseSampler):
 
     def _graph_for(self, x: torch.Tensor):
         """The replay state for this (batch shape, coefficients, model state): static buffers + the step body; the graph
-        itself is captured by ``_sample_graph`` behind the first eager step."""
+        itself is captured by ``_chain_host.sample_graph`` behind the first eager step."""
         a, sq, coef = em_coefficients(self.get_scheduled_value("step_size"), self.get_scheduled_value("noise_scale"))
         key = (
             tuple(x.shape), x.device, (a, sq, coef), self._clamp_args(),
@@ -420,33 +315,6 @@ class LangevinDynamics(BaseSampler):
         self._step_graph = {"key": key, "graph": None, "state": state, "rng": rng, "body": body}
         return self._step_graph
 
-    def _sample_graph(self, x, n_steps, thin, traj, diag, want_traj, want_diag, generator):
-        x = _lib.dense_f32(x)
-        n = x.shape[0]
-        g = self._graph_for(x)
-        seed, step0 = _rng.reserve(generator, x.device, n_steps)
-        as_i64 = lambda v: v - (1 << 64) if v >= (1 << 63) else v  # noqa: E731  (bit pattern of a uint64)
-        g["state"].copy_(x)
-        g["rng"].copy_(torch.tensor([as_i64(seed), as_i64(step0)], dtype=torch.int64), non_blocking=True)
-        state, keep = g["state"], 0
-        for i in range(n_steps):
-            _replay_or_step(self, g, first=(i == 0), more=(i + 1 < n_steps))
-            if (i + 1) % thin == 0:
-                if traj is not None:
-                    traj[:, keep] = state
-                if diag is not None:
-                    if n > 1:
-                        diag["mean"][keep] = state.mean(dim=0)
-                        diag["var"][keep] = state.var(dim=0, unbiased=False).clamp_(min=1e-10, max=1e10)
-                    else:
-                        diag["mean"][keep] = state.squeeze(0)
-                        diag["var"][keep].zero_()
-                    diag["energy"][keep] = self._model_energy(state, {}).mean()
-                keep += 1
-        self.advance_schedulers(n_steps)
-        out = traj if want_traj else state.clone()
-        return (out, diag) if want_diag else out
-
     # ---------------------------------------------------------------------------------
     # route: k-fused HIP kernel
     # ---------------------------------------------------------------------------------
@@ -460,19 +328,6 @@ class LangevinDynamics(BaseSampler):
         etas, sigmas = s_eta.preview(k), s_sig.preview(k)
         return False, [em_coefficients(e, s) for e, s in zip(etas, sigmas)]
 
-    def _coef_table(self, rows, device) -> Optional[torch.Tensor]:
-        """Device table ``float[k][4]`` of a non-constant schedule, kept for the next call with the same schedule
-        (a training loop calls ``sample`` with an unchanged scheduler thousands of times)."""
-        if len(rows) == 1:
-            return None
-        key = (device, tuple(rows))
-        cached = getattr(self, "_table_cache", None)
-        if cached is None or cached[0] != key:
-            host = torch.tensor([(r[0], r[1], r[2], 0.0) for r in rows], dtype=torch.float32)
-            cached = (key, host.to(device, non_blocking=True))
-            self._table_cache = cached
-        return cached[1]
-
     def _launch_chain(self, spec_c, x, n, dim, rows, row0, k, thin, traj, seed, step, stream, table=None, records=None, src=None):
         """One ``ebm_langevin_chain_f32`` launch for steps [row0, row0+k) of ``rows``.  With ``src`` (the first launch of an
         out-of-place call, plain Euler-Maruyama only) the chains start from ``src`` and ``x`` is only written:
@@ -483,7 +338,7 @@ class LangevinDynamics(BaseSampler):
             tab = None
         else:
             a, sq, coef = rows[row0]
-            tab = (self._coef_table(rows, x.device) if table is None else table)[row0 : row0 + k]
+            tab = (schedule_table(self, rows, x.device) if table is None else table)[row0 : row0 + k]
         coords = getattr(self, "_graph_coords", None)
         if coords is not None:  # being captured in a HIP graph: `step` is an offset from the device-resident coordinates
             _lib.call(
@@ -543,7 +398,7 @@ class LangevinDynamics(BaseSampler):
                 src, state = state, torch.empty_like(state, memory_format=torch.contiguous_format)
             else:
                 state = state.clone()
-        traj, diag = self._new_outputs(x, n_kept, want_traj, want_diag)
+        traj, diag = new_outputs(self, x.shape, n_kept, want_traj, want_diag)
         _, rows = self._coef_rows(n_steps)
         if coords is not None:
             # utils.graphed_step is capturing this call: coordinates come from device memory (ebm_langevin_chain_dev_f32)
@@ -566,98 +421,49 @@ class LangevinDynamics(BaseSampler):
                 # one launch for the whole call; thinned rows are stored by the kernel
                 self._launch_chain(spec_c, state, n, dim, rows, 0, n_steps, thin, traj, seed, step0, stream, src=src)
             elif layout is not None:
-                self._fused_with_records(spec_c, state, n, dim, rows, n_steps, thin, traj, diag, layout, seed, step0, stream, src=src)
+                self._fused_with_records(state, n_steps, thin, traj, diag, layout, stream,
+                                         self._launcher(spec_c, state, rows, thin, seed, step0, stream, src))
             else:
-                self._fused_with_state_passes(spec_c, state, n, dim, rows, n_steps, thin, traj, diag, seed, step0, stream, src=src)
+                self._fused_with_state_passes(spec_c, state, n_steps, thin, traj, diag, stream,
+                                              self._launcher(spec_c, state, rows, thin, seed, step0, stream, src))
         self.advance_schedulers(n_steps)
         out = traj if want_traj else state
         return (out, diag) if want_diag else out
 
-    def _fused_with_records(self, spec_c, state, n, dim, rows, n_steps, thin, traj, diag, layout, seed, step0, stream, src=None):
-        """Diagnostics from inside the chain launch (include/ebm_hip.h: ``diag_partials``): every workgroup stores
-        one record of its chains' partial sums per kept step, ``ebm_diag_finish_f32`` merges them.  One chain
-        launch + one merge launch per call (several only when the records of all kept steps would not fit
-        ``DIAG_RECORD_BYTES``)."""
-        n_blocks, slots, block_elems = layout
-        n_kept = n_steps // thin
+    def _launcher(self, spec_c, state, rows, thin, seed, step0, stream, src):
+        """``launch(t0, steps, traj_piece, records, first)`` of the drivers of a call with diagnostics: steps
+        ``[t0, t0 + steps)`` of the call on ``state``, the first launch alone starting from ``src``."""
+        n, dim = state.shape
+
+        def launch(t0, steps, piece, records, first):
+            self._launch_chain(spec_c, state, n, dim, rows, t0, steps, thin, piece, seed, step0 + t0, stream,
+                               records=records, src=src if first else None)
+
+        return launch
+
+    def _fused_with_records(self, state, n_steps, thin, traj, diag, layout, stream, launch):
+        """Diagnostics from inside the chain launch (``_chain_host.run_with_records``)."""
         # slots > dim: PACKED rows (a Gaussian whose width the matrix-layout kernel does not take as is: csrc/gauss_mfma.hip,
         # gauss_pack_factor) -- `pack` consecutive chains are one row of width pack * dim; the records and the merge are those of
         # n / pack rows, and the `pack` columns of every coordinate are pooled afterwards
-        pack = slots // dim if slots > dim else 1
-        m_n, m_dim = n // pack, dim * pack
-        rec_floats = n_blocks * (2 * slots + 8)
-        chunk = max(1, min(n_kept, self.DIAG_RECORD_BYTES // (4 * rec_floats)))
-        records, work = _record_scratch(self, state.device, stream, chunk * rec_floats, chunk * (3 * m_dim + 3))
-        if pack > 1:
-            p_mean = torch.empty(chunk, m_dim, dtype=torch.float32, device=state.device)
-            p_var = torch.empty_like(p_mean)
-            p_energy = torch.empty(chunk, dtype=torch.float32, device=state.device)
-        done_keep, done_steps = 0, 0
-        while done_keep < n_kept:
-            kk = min(chunk, n_kept - done_keep)
-            steps = kk * thin
-            if done_keep + kk == n_kept:
-                steps = n_steps - done_steps  # the trailing n_steps % thin steps ride along (no kept step among them)
-            whole = traj is not None and kk == n_kept
-            piece = traj if (traj is None or whole) else torch.empty(n, kk, dim, dtype=torch.float32, device=state.device)
-            self._launch_chain(spec_c, state, n, dim, rows, done_steps, steps, thin, piece, seed, step0 + done_steps, stream,
-                               records=records, src=src)
-            src = None  # the first launch only: every later one continues in place on `state`
-            if traj is not None and not whole:
-                traj[:, done_keep : done_keep + kk] = piece
-            sl = slice(done_keep, done_keep + kk)
-            if pack == 1:
-                _lib.call(
-                    "ebm_diag_finish_f32", _lib.ptr(records), kk, n_blocks, slots, block_elems, n, dim,
-                    _lib.ptr(diag["mean"][sl]), _lib.ptr(diag["var"][sl]), _lib.ptr(diag["energy"][sl]), None, _lib.ptr(work), stream,
-                )
-            else:
-                _lib.call(
-                    "ebm_diag_finish_f32", _lib.ptr(records), kk, n_blocks, slots, block_elems, m_n, m_dim,
-                    _lib.ptr(p_mean), _lib.ptr(p_var), _lib.ptr(p_energy), None, _lib.ptr(work), stream,
-                )
-                # pool the `pack` equally sized groups of every coordinate: within-group variance + variance of the group means
-                gm = p_mean[:kk].view(kk, pack, dim).double()
-                mean = gm.mean(dim=1)
-                var = p_var[:kk].view(kk, pack, dim).double().mean(dim=1) + (gm - mean.unsqueeze(1)).square().mean(dim=1)
-                diag["mean"][sl] = mean.to(torch.float32)
-                diag["var"][sl] = var.to(torch.float32).clamp_(min=1e-10, max=1e10)
-                diag["energy"][sl] = p_energy[:kk] / pack  # a packed row's energy is the sum of its chains'
-            done_keep += kk
-            done_steps += steps
-        _record_scratch_done(self)
+        slots, dim = layout[1], state.shape[1]
+        run_with_records(self, state, n_steps, thin, traj, diag, layout, stream, launch, pack=slots // dim if slots > dim else 1)
 
-    def _fused_with_state_passes(self, spec_c, state, n, dim, rows, n_steps, thin, traj, diag, seed, step0, stream, src=None):
+    def _fused_with_state_passes(self, spec_c, state, n_steps, thin, traj, diag, stream, launch):
         """Diagnostics for the configurations without in-kernel records (the matrix-layout kernels of the MLP
-        energy, rows that neither divide nor are divided by the flat kernel's 1024-element blocks): one launch per
-        ``thin`` steps, then the column-statistics and energy kernels on the state."""
-        n_kept = n_steps // thin
-        work = torch.zeros(2 * dim + 1, dtype=torch.float64, device=state.device)  # the kernel leaves it zeroed
+        energy, rows that neither divide nor are divided by the flat kernel's 1024-element blocks): the energy pass
+        of ``_chain_host.run_with_state_passes``."""
+        n, dim = state.shape
         energy = torch.empty(n, dtype=torch.float32, device=state.device)
         # a dense Gaussian above 128 dims: ebm_energy_grad_f32 is the lane-group mat-vec there (2 TFLOP/s: at 2^17 x 256 one
         # energy pass would cost more than the 20 chain steps before it)
         from ..core.energies import GaussianModel
         wide_gaussian = type(self.model) is GaussianModel and dim > GaussianModel.CLOSED_FORM_GRADIENT_ABOVE
-        done = 0
-        for keep in range(n_kept):
-            self._launch_chain(spec_c, state, n, dim, rows, done, thin, thin, None, seed, step0 + done, stream, src=src)
-            src = None  # the first launch only: every later one continues in place on `state`
-            done += thin
-            if traj is not None:
-                traj[:, keep] = state
-            if n > 1:
-                _lib.call(
-                    "ebm_chain_stats_f32",
-                    _lib.ptr(state), n, dim, _lib.ptr(diag["mean"][keep]), _lib.ptr(diag["var"][keep]),
-                    _lib.ptr(work), stream,
-                )
-            else:
-                diag["mean"][keep] = state[0]
-                diag["var"][keep].zero_()
+
+        def mean_energy():
             if wide_gaussian:
-                diag["energy"][keep] = self._model_energy(state, {}).mean()   # one library GEMM (GaussianModel.forward, wide CUDA batches)
-            else:
-                _lib.call("ebm_energy_grad_f32", spec_c, _lib.ptr(state), n, dim, _lib.ptr(energy), None, stream)
-                diag["energy"][keep] = energy.mean()
-        if done < n_steps:
-            self._launch_chain(spec_c, state, n, dim, rows, done, n_steps - done, thin, None, seed, step0 + done, stream)
+                return self._model_energy(state, {}).mean()   # one library GEMM (GaussianModel.forward, wide CUDA batches)
+            _lib.call("ebm_energy_grad_f32", spec_c, _lib.ptr(state), n, dim, _lib.ptr(energy), None, stream)
+            return energy.mean()
+
+        run_with_state_passes(state, n_steps, thin, traj, diag, stream, launch, mean_energy)

@@ -38,6 +38,7 @@ from .. import _lib, _rng
 from ..core.energies import BaseModel, FusedSpec, fused_spec_for
 from ..core.sampler_base import BaseSampler
 from ..core.schedules import BaseScheduler
+from ._chain_host import kept_statistics, new_outputs, record_kept
 
 
 def ladder_coefficients(noise_scale: float, temperatures: Sequence[float]) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -57,8 +58,7 @@ def lanes_per_row(dim: int) -> int:
 
 
 class _LadderSampler(BaseSampler):
-    """What the replica-exchange samplers share: the ladder's validation, the start conventions of ``sample()`` and the
-    slot-0 statistics of the kept states."""
+    """What the replica-exchange samplers share: the ladder's validation and the start conventions of ``sample()``."""
 
     def _init_ladder(self, temperatures: Sequence[float], swap_every: int) -> None:
         temps = tuple(float(t) for t in temperatures)
@@ -89,44 +89,6 @@ class _LadderSampler(BaseSampler):
         elif x.ndim != 3 or x.shape[1] != R:
             raise ValueError(f"x must be [n, dim] or [n, {R}, dim], got {tuple(x.shape)}")
         return x.contiguous()
-
-    def _new_diag(self, n_kept: int, dim: int, like: torch.Tensor) -> Dict[str, torch.Tensor]:
-        return {
-            "mean": torch.empty(n_kept, dim, dtype=like.dtype, device=like.device),
-            "var": torch.empty(n_kept, dim, dtype=like.dtype, device=like.device),
-            "energy": torch.empty(n_kept, dtype=like.dtype, device=like.device),
-        }
-
-    def _eager_keep(self, cold: torch.Tensor, keep: int, traj, diag) -> None:
-        """Record slot 0 (``cold`` ``[n, dim]``) as kept state ``keep`` of the eager routes."""
-        if traj is not None:
-            traj[:, keep] = cold
-        if diag is not None:
-            if cold.shape[0] > 1:
-                diag["mean"][keep] = cold.mean(dim=0)
-                diag["var"][keep] = cold.var(dim=0, unbiased=False).clamp_(min=1e-10, max=1e10)
-            else:
-                diag["mean"][keep] = cold.squeeze(0)
-                diag["var"][keep].zero_()
-            diag["energy"][keep] = self._model_energy(cold.contiguous(), {}).mean()
-
-    def _kept_statistics(self, spec_c, traj: torch.Tensor, diag: Dict[str, torch.Tensor], stream) -> None:
-        """mean / var / energy of slot 0 from the kept states, with the column-statistics and energy kernels."""
-        n, n_kept, dim = traj.shape
-        kept = traj.transpose(0, 1).contiguous()  # [n_kept, n, dim]: one dense population per kept step
-        energy = torch.empty(n_kept, n, dtype=torch.float32, device=traj.device)
-        _lib.call("ebm_energy_grad_f32", spec_c, _lib.ptr(kept), n_kept * n, dim, _lib.ptr(energy), None, stream)
-        diag["energy"].copy_(energy.mean(dim=1))
-        if n == 1:
-            diag["mean"].copy_(kept[:, 0])
-            diag["var"].zero_()
-            return
-        work = torch.zeros(2 * dim + 1, dtype=torch.float64, device=traj.device)  # the kernel leaves it zeroed
-        for keep in range(n_kept):
-            _lib.call(
-                "ebm_chain_stats_f32",
-                _lib.ptr(_lib.dense_f32(kept[keep])), n, dim, _lib.ptr(diag["mean"][keep]), _lib.ptr(diag["var"][keep]), _lib.ptr(work), stream,
-            )
 
 
 class ReplicaExchangeLangevin(_LadderSampler):
@@ -222,8 +184,8 @@ class ReplicaExchangeLangevin(_LadderSampler):
         n, R, dim = x.shape
         n_kept = n_steps // thin
         x = x.clone()
-        traj = torch.empty(n, n_kept, dim, dtype=x.dtype, device=x.device) if want_traj else None
-        diag = self._new_diag(n_kept, dim, x) if want_diag else None
+        traj, diag = new_outputs(x, (n, dim), n_kept, want_traj, want_diag)
+        cold_energy = lambda cold: self._model_energy(cold.contiguous(), {})  # noqa: E731
         tried = torch.zeros(R - 1, dtype=torch.float64)
         took = torch.zeros(R - 1, dtype=torch.float64)
         keep = event = 0
@@ -250,7 +212,7 @@ class ReplicaExchangeLangevin(_LadderSampler):
                         x[:, r + 1] = torch.where(ok[:, None], lower, x[:, r + 1])
                     event += 1
                 if (s + 1) % thin == 0:
-                    self._eager_keep(x[:, 0], keep, traj, diag)
+                    record_kept(x[:, 0], keep, traj, diag, cold_energy)
                     keep += 1
         if diag is not None:
             diag["swap_acceptance"] = (took / tried).to(device=x.device, dtype=x.dtype)
@@ -290,9 +252,9 @@ class ReplicaExchangeLangevin(_LadderSampler):
         self.advance_schedulers(n_steps)
         diag = None
         if want_diag:
-            diag = self._new_diag(n_kept, dim, state)
+            diag = new_outputs(state, (n, dim), n_kept, False, True)[1]
             if n > 0 and n_kept > 0:
-                self._kept_statistics(spec_c, traj, diag, stream)
+                kept_statistics(spec_c, traj, diag, stream)
             c = (counts.to(torch.int64) & 0xFFFFFFFF).to(torch.float64)  # (uint32 counters in an int32 tensor)
             diag["swap_acceptance"] = (c[R - 1 :] / c[: R - 1]).to(torch.float32)
         return state, (traj if want_traj else None), diag
@@ -423,8 +385,8 @@ class ReplicaExchangeHMC(_LadderSampler):
         n, R, dim = x.shape
         n_kept = n_steps // thin
         x = x.clone()
-        traj = torch.empty(n, n_kept, dim, dtype=x.dtype, device=x.device) if want_traj else None
-        diag = self._new_diag(n_kept, dim, x) if want_diag else None
+        traj, diag = new_outputs(x, (n, dim), n_kept, want_traj, want_diag)
+        cold_energy = lambda cold: self._model_energy(cold.contiguous(), {})  # noqa: E731
         sqrt_temp, beta = (v.to(x.device, x.dtype) for v in hmc_ladder_coefficients(self.temperatures))
         sqrt_temp = sqrt_temp.view(1, R, 1)
         accepted = torch.zeros(R, dtype=torch.float64)
@@ -471,7 +433,7 @@ class ReplicaExchangeHMC(_LadderSampler):
                         x[:, r + 1] = torch.where(ok[:, None], lower, x[:, r + 1])
                     event += 1
                 if (t + 1) % thin == 0:
-                    self._eager_keep(x[:, 0], keep, traj, diag)
+                    record_kept(x[:, 0], keep, traj, diag, cold_energy)
                     keep += 1
         if diag is not None:
             diag["swap_acceptance"] = (took / tried).to(device=x.device, dtype=x.dtype)
@@ -515,9 +477,9 @@ class ReplicaExchangeHMC(_LadderSampler):
         self.advance_schedulers(n_steps)
         diag = None
         if want_diag:
-            diag = self._new_diag(n_kept, dim, state)
+            diag = new_outputs(state, (n, dim), n_kept, False, True)[1]
             if n > 0 and n_kept > 0:
-                self._kept_statistics(spec_c, traj, diag, stream)
+                kept_statistics(spec_c, traj, diag, stream)
             c = (swaps.to(torch.int64) & 0xFFFFFFFF).to(torch.float64)
             diag["swap_acceptance"] = (c[R - 1 :] / c[: R - 1]).to(torch.float32)
             got = (accepts.to(torch.int64) & 0xFFFFFFFF).to(torch.float64)
