@@ -558,6 +558,54 @@ EBM_API int ebm_kinetic_chain_f32(const ebm_energy_t* energy, float* x, float* v
                                   int32_t k_steps, double h, double gamma, double temperature, int32_t draw_v0, int32_t thin,
                                   float* traj, const float* noise, uint64_t seed, uint64_t offset, void* stream);
 
+/*
+ * Generalized HMC (Horowitz 1991; Metropolis-adjusted kinetic Langevin): n_mh transitions of a walker per chain that carries a
+ * velocity beside its position, in ONE launch (an addition to ABI 9: nothing else moved).  Each transition refreshes the
+ * velocity partially, runs a short Metropolis-corrected leapfrog trajectory and flips the velocity on a reject: exp(-E / T) is
+ * sampled exactly for every step size, as by ebm_hmc_chain_f32, and with weak friction the walker keeps its direction across
+ * transitions, as ebm_kinetic_chain_f32's does.  Unit mass, step eps > 0, n_leapfrog = L >= 1 steps, friction gamma > 0 (+inf
+ * allowed), temperature T > 0 (beta = 1 / T).
+ *
+ * Constants.  The entry forms them in double and rounds each once to fp32 (eps itself too):
+ *     c1 = exp(-gamma eps L);   c2 = sqrt(T * (-expm1(-2 gamma eps L)));   sqrt_temp = sqrt(T);   beta = 1 / T
+ * gamma = +inf gives c1 = 0 and c2 = sqrt_temp exactly: a full refresh, the transition of ebm_hmc_chain_f32.
+ *
+ * A chain carries x, v, E(x) and the clamped force at x from the load to the one store; the last two come from the
+ * pseudo-transition of ebm_hmc_chain_f32's lane-group kernel (one evaluation in front of the first transition).
+ * Transition t = 0 .. n_mh - 1:
+ *     v  = c1 * v + c2 * z_t                       (O)  two products and a sum, each rounded on its own
+ *     u  = the uniform of this chain
+ *     H0 = clamp(E(x), +-1e10) + clamp(0.5 sum v^2, 0, 1e10)
+ *     (x', v') = n_leapfrog safe-mode leapfrog steps of size eps from (x, v): the trajectory of ebm_hmc_chain_f32, identity
+ *                mass (the force clamp +-1e6, the NaN scrubs, the carried energy and force, merged kicks, literal fallback)
+ *     H1 = clamp(E(x'), +-1e10) + clamp(0.5 sum v'^2, 0, 1e10)
+ *     d  = clamp(beta * (H0 - H1), +-50);  a = min(1, exp d);  accepted iff u < a (a NaN rejects)
+ *     accepted:  (x, v, E, force) = (x', v', E', force')
+ *     rejected:  x, E and the force stay;  v = -(the v after O)                                  the flip
+ *
+ * Draws.  A call owns the Philox steps offset .. offset + 2 n_mh.  z_t is the normal field at step offset + 1 + 2 t, element
+ * chain * dim + col; u the uniform field at step offset + 2 + 2 t, element chain.  draw_v0 != 0: v is output only and the walk
+ * starts from sqrt_temp * z, z the normal field at step offset (also when draws are injected); draw_v0 == 0: v is read --
+ * velocities that persist across calls.  noise: NULL, or float[n_mh][n_chains][dim] in place of z_t; u: NULL, or
+ * float[n_mh][n_chains] in place of the uniforms; either may be given without the other.
+ *
+ * Outputs.  x and v are updated in place and stored once.  traj: NULL, or float[n_chains][n_mh / thin][dim], the position
+ * after transition t whenever (t + 1) % thin == 0.  accept_mask: NULL, or uint8[n_mh][n_chains] (1 = accepted).  Slots of a
+ * lane that hold no column never reach memory.
+ *
+ * Two calls equal one: (n1, offset) then (n2, offset + 2 n1) with draw_v0 = 0 produces the bits of one call of n1 + n2 -- the
+ * carried energy and force are re-evaluated by the evaluation the last leapfrog step ended on.
+ *
+ * Limits: every analytic energy except EBM_ENERGY_MLP (EBM_EKIND); 1 <= dim <= 256, one vector per lane (EBM_EDIM, in front
+ * of any device access); constants only: no tables, no mass matrix, no diagnostics records; 64-bit row indices.
+ * EBM_EINVAL with no buffer touched: a NULL energy, x or v; n_mh < 1, n_leapfrog < 1 or thin < 1; eps, gamma or temperature
+ * not positive, or NaN (eps and temperature must be finite).  An empty call (n_chains == 0) returns 0 behind these checks.
+ */
+EBM_API int ebm_ghmc_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t n_mh,
+                               int32_t n_leapfrog, double eps, double gamma, double temperature, int32_t draw_v0,
+                               int32_t thin, float* traj, uint8_t* accept_mask, const float* noise, const float* u,
+                               uint64_t seed, uint64_t offset, void* stream);
+
 /* The accept step with the RNG coordinates in DEVICE memory (rng_state = {seed, step}; the uniforms
  * are drawn at step rng_state[1] + step_delta): the graph-capturable form, see
  * ebm_langevin_step_dev_f32.  No injected-uniform form. */

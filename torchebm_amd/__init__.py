@@ -21,6 +21,7 @@ from .integrators import EulerMaruyamaIntegrator, LeapfrogIntegrator  # noqa: F4
 from .losses import ContrastiveDivergence, EnergyMatchingContrastive  # noqa: F401
 from .samplers import (  # noqa: F401
     AnnealedImportanceSampling,
+    GeneralizedHMC,
     HamiltonianMonteCarlo,
     LangevinDynamics,
     ReplicaExchangeHMC,

@@ -550,6 +550,37 @@ int ebm_kinetic_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_
   return kinetic_chain_launch(q, (hipStream_t)stream);
 }
 
+int ebm_ghmc_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t n_mh,
+                       int32_t n_leapfrog, double eps, double gamma, double temperature, int32_t draw_v0, int32_t thin,
+                       float* traj, uint8_t* accept_mask, const float* noise, const float* u, uint64_t seed, uint64_t offset,
+                       void* stream) {
+  const char* who = "ebm_ghmc_chain_f32";
+  if (energy && energy->kind == EBM_ENERGY_MLP)
+    return fail(EBM_EKIND, "%s: the MLP energy has no generalized-HMC kernel (the sampler's eager route takes it)", who);
+  if (int r = check_energy(energy, dim, who)) return r;
+  if (int r = ghmc_check_geometry(dim)) return r;  // (in front of check_state: dim < 1 is EBM_EDIM here, as dim > 256 is)
+  if (int r = check_state(x, n_chains, dim, who)) return r;
+  if (!v) return fail(EBM_EINVAL, "%s: velocity pointer is NULL", who);
+  if (n_mh < 1 || n_leapfrog < 1 || thin < 1)
+    return fail(EBM_EINVAL, "%s: n_mh=%d n_leapfrog=%d thin=%d (all must be >= 1)", who, n_mh, n_leapfrog, thin);
+  // (gamma = +inf is allowed: a full refresh, the HMC transition)
+  if (!(eps > 0.0) || !(gamma > 0.0) || !(temperature > 0.0) || !std::isfinite(eps) || !std::isfinite(temperature))
+    return fail(EBM_EINVAL, "%s: eps=%g gamma=%g temperature=%g (all must be positive; eps and temperature finite)", who, eps, gamma,
+                temperature);
+  if (n_chains == 0) return 0;
+  if (!aligned16(v) || (traj && !aligned16(traj)) || (noise && !aligned16(noise)))
+    return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  // the constants of the refresh over one trajectory's time eps L: formed in double, each rounded once
+  const double span = gamma * eps * (double)n_leapfrog;
+  const float sqrt_temp = (float)sqrt(temperature);
+  const float c1 = std::isinf(gamma) ? 0.0f : (float)exp(-span);
+  const float c2 = std::isinf(gamma) ? sqrt_temp : (float)sqrt(temperature * (-expm1(-2.0 * span)));
+  const float beta = (float)(1.0 / temperature);
+  const GhmcChainReq q{*energy, x, v, n_chains, dim, n_mh, n_leapfrog, (float)eps, c1, c2, sqrt_temp, beta, draw_v0 != 0, thin, traj,
+                       accept_mask, noise, u, seed, offset};
+  return ghmc_chain_launch(q, (hipStream_t)stream);
+}
+
 int ebm_leapfrog_kick_drift_f32(const float* x, const float* p, const float* force, float* x_new,
                                 float* p_half, int64_t n_chains, int32_t dim, float eps,
                                 int32_t mass_kind, double mass_scalar, const float* mass_diag,

@@ -159,6 +159,26 @@ struct KineticChainReq {
   int32_t n_kept() const { return k_steps / thin; }
 };
 
+struct GhmcChainReq {
+  const ebm_energy_t& e;
+  float* x;                // [n_chains, dim], in/out
+  float* v;                // [n_chains, dim]: in/out, output only with draw_v0
+  int64_t n_chains;
+  int32_t dim, n_mh, n_leapfrog;
+  // eps, exp(-gamma eps L), sqrt(T (1 - exp(-2 gamma eps L))), sqrt(T), 1 / T: formed in double, rounded once
+  float eps, c1, c2, sqrt_temp, beta;
+  bool draw_v0;
+  int32_t thin;
+  float* traj;             // [n_chains, n_kept(), dim] or null
+  uint8_t* accept_mask;    // [n_mh, n_chains] or null
+  const float* noise;      // [n_mh, n_chains, dim] or null
+  const float* u;          // [n_mh, n_chains] or null
+  uint64_t seed, offset;
+
+  RngKey key() const { return RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)}; }
+  int32_t n_kept() const { return n_mh / thin; }
+};
+
 // The fields the row-major Langevin argument structs share (GaussArgs, BigArgs, RowChainArgs, WideArgs).
 template <class Args>
 inline void fill_langevin(Args& a, const LangevinChainReq& q) {
@@ -283,5 +303,11 @@ int moments_check_geometry(int32_t dim);  // 0, or the refusal (dim > 256)
 // ---------------------------------------------------------------------------------
 int kinetic_chain_launch(const KineticChainReq&, hipStream_t);
 int kinetic_check_geometry(int32_t dim);  // 0, or the refusal (dim > 256)
+
+// ---------------------------------------------------------------------------------
+// Generalized HMC (ghmc.hip: the kinetic walker with a partial momentum refresh, a Metropolis-corrected trajectory and the flip)
+// ---------------------------------------------------------------------------------
+int ghmc_chain_launch(const GhmcChainReq&, hipStream_t);
+int ghmc_check_geometry(int32_t dim);  // 0, or the refusal (dim > 256)
 
 }  // namespace ebm

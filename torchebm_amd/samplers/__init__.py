@@ -2,6 +2,7 @@
 
 from .ais import AISResult, AnnealedImportanceSampling
 from .descent import GradientDescentSampler, NesterovSampler
+from .ghmc import GeneralizedHMC
 from .hamiltonian import HamiltonianMonteCarlo
 from .kinetic import UnderdampedLangevin
 from .langevin import LangevinDynamics
@@ -10,4 +11,4 @@ from .tempering import ReplicaExchangeHMC, ReplicaExchangeLangevin
 
 __all__ = ["LangevinDynamics", "HamiltonianMonteCarlo", "GradientDescentSampler", "NesterovSampler",
            "ReplicaExchangeLangevin", "ReplicaExchangeHMC", "AnnealedImportanceSampling", "AISResult", "ChainMoments", "RunningMoments",
-           "UnderdampedLangevin"]
+           "UnderdampedLangevin", "GeneralizedHMC"]

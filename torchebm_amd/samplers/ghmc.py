@@ -1,0 +1,253 @@
+r"""Generalized HMC (Horowitz 1991), the Metropolis-adjusted kinetic Langevin sampler: :class:`GeneralizedHMC`.
+
+A chain carries a velocity ``v`` beside its position ``x`` (unit mass, friction ``gamma``, temperature ``T``: the target is
+``exp(-E / T)``).  One transition with step ``eps`` and ``L`` leapfrog steps:
+
+.. math::
+    v \leftarrow e^{-\gamma \epsilon L} v + \sqrt{T (1 - e^{-2 \gamma \epsilon L})}\,\xi,\quad
+    (x', v') = \mathrm{leapfrog}^L_\epsilon(x, v),\quad
+    a = \min(1, e^{(H(x, v) - H(x', v')) / T}),\quad
+    (x, v) \leftarrow (x', v') \text{ with probability } a, \text{ else } (x, -v)
+
+The partial refresh keeps ``N(0, T)``, the trajectory with its Metropolis decision and the flip keeps ``exp(-H / T)``: the
+chain samples ``exp(-E / T)`` exactly for every step size, as ``HamiltonianMonteCarlo`` does (``friction=inf`` IS that
+sampler's transition), and with weak friction it keeps its direction across transitions, as ``UnderdampedLangevin`` does --
+which is unadjusted and leaves a step-size bias.
+
+Two execution routes, chosen once per ``sample()`` call (``_route``):
+
+``fused``  CUDA fp32 2-D state, no autocast, one of the analytic energies (not the MLP), ``dim <= 256`` and a constant step size:
+           the whole call -- start velocities, refreshes, trajectories, decisions, Philox draws, thinned trajectory, accept mask
+           -- is ONE launch of ``ebm_ghmc_chain_f32`` (include/ebm_hip.h states the recurrence exactly; docs/design/ghmc.md
+           the kernel).
+``eager``  everything else (CPU, any other ``BaseModel``, a scheduler on ``step_size``, wider rows): the same recurrence in
+           torch ops around ``model`` / ``model.gradient`` with the clamps of ``HamiltonianMonteCarlo``'s eager transition,
+           drawing ``randn(n, dim)`` for the start velocities (only when none are passed) and ``randn(n, dim)``, ``rand(n)``
+           per transition.
+
+A fused-eligible call never falls back to eager: a missing library or a failing launch raises.
+"""
+
+from __future__ import annotations
+
+import math
+from typing import Optional, Tuple, Union
+
+import torch
+
+from .. import _lib, _rng
+from ..core.energies import BaseModel, FusedSpec, fused_spec_for
+from ..core.sampler_base import BaseSampler
+from ..core.schedules import BaseScheduler
+from ._chain_host import kept_statistics, new_outputs, record_kept
+
+FUSED_MAX_DIM = 256  # one vector per lane (csrc/ghmc.hip)
+
+
+def ghmc_constants(eps: float, n_leapfrog: int, friction: float, temperature: float,
+                   dtype: torch.dtype = torch.float32) -> Tuple[float, float, float, float]:
+    """``(exp(-gamma eps L), sqrt(T (1 - exp(-2 gamma eps L))), sqrt(T), 1 / T)``: formed in double, each rounded once to
+    ``dtype`` (the constants ``ebm_ghmc_chain_f32`` forms from the same numbers); ``friction=inf`` gives ``c1 = 0`` and
+    ``c2 = sqrt(T)`` exactly."""
+    sqrt_temp = math.sqrt(temperature)
+    if math.isinf(friction):
+        c1, c2 = 0.0, sqrt_temp
+    else:
+        span = friction * eps * n_leapfrog
+        c1, c2 = math.exp(-span), math.sqrt(temperature * (-math.expm1(-2.0 * span)))
+    return tuple(torch.tensor((c1, c2, sqrt_temp, 1.0 / temperature), dtype=torch.float64).to(dtype).tolist())
+
+
+class GeneralizedHMC(BaseSampler):
+    """Generalized HMC: partial momentum refresh, a Metropolis-corrected leapfrog trajectory, a momentum flip on a reject.
+
+    Args:
+        model: energy model to sample from.
+        step_size: leapfrog step ``eps``, a float or (eager route) a ``BaseScheduler``.
+        n_leapfrog_steps: leapfrog steps ``L >= 1`` per transition.
+        friction: friction ``gamma > 0``; the velocity keeps ``exp(-gamma eps L)`` of itself per transition, ``inf`` is HMC.
+        temperature: temperature ``T > 0``; the chains sample ``exp(-E / T)``.
+        dtype, device: where the chains live.
+    """
+
+    def __init__(
+        self,
+        model: BaseModel,
+        step_size: Union[float, BaseScheduler] = 1e-2,
+        n_leapfrog_steps: int = 1,
+        friction: float = 1.0,
+        temperature: float = 1.0,
+        dtype: torch.dtype = torch.float32,
+        device: Optional[Union[str, torch.device]] = None,
+    ):
+        super().__init__(model=model, dtype=dtype, device=device)
+        self._register_param("step_size", step_size, positive=True)
+        if int(n_leapfrog_steps) != n_leapfrog_steps or n_leapfrog_steps < 1:
+            raise ValueError("n_leapfrog_steps must be an integer >= 1")
+        if not friction > 0:  # (inf is allowed: a full refresh)
+            raise ValueError("friction must be positive")
+        if not (temperature > 0 and math.isfinite(temperature)):
+            raise ValueError("temperature must be positive")
+        self.n_leapfrog_steps = int(n_leapfrog_steps)
+        self.friction = float(friction)
+        self.temperature = float(temperature)
+
+    # ---------------------------------------------------------------------------------
+    # routing: decided here and nowhere else
+    # ---------------------------------------------------------------------------------
+    def _route(self, x: torch.Tensor, model_kwargs=None) -> Tuple[str, Optional[FusedSpec]]:
+        # (model_kwargs: unused -- the signature of the other samplers' _route, which the tests' CPU stand-in replaces)
+        if not x.is_cuda or x.dtype != torch.float32 or x.ndim != 2:
+            return "eager", None
+        if not self.schedulers["step_size"].is_constant():
+            return "eager", None
+        if self.use_mixed_precision and self.autocast_available:
+            return "eager", None
+        spec = fused_spec_for(self.model, x, None)
+        if spec is None or spec.kind == _lib.ENERGY_MLP or x.shape[1] > FUSED_MAX_DIM:
+            return "eager", None
+        return "fused", spec
+
+    # ---------------------------------------------------------------------------------
+    # public API
+    # ---------------------------------------------------------------------------------
+    @torch.no_grad()
+    def sample(
+        self,
+        x: Optional[torch.Tensor] = None,
+        dim: Optional[Union[int, Tuple[int, ...]]] = None,
+        n_steps: int = 100,
+        n_samples: int = 1,
+        thin: int = 1,
+        return_trajectory: bool = False,
+        return_diagnostics: bool = False,
+        reset_schedulers: bool = True,
+        *,
+        velocity: Optional[torch.Tensor] = None,
+        return_velocity: bool = False,
+        generator: Optional[torch.Generator] = None,
+    ):
+        """Run ``n_steps`` transitions.
+
+        ``velocity``: the start velocities, shaped as ``x`` (as a call with ``return_velocity=True`` returned them: continue
+        that run); ``None`` draws them from ``N(0, T I)``.
+
+        Returns the final positions ``[n, *shape]`` (or, with ``return_trajectory``, the kept positions
+        ``[n, n_steps // thin, *shape]``); with ``return_diagnostics`` a dict follows, holding ``"mean"`` / ``"var"``
+        (``[n_kept, *shape]``, biased variance clamped to [1e-10, 1e10]), ``"energy"`` and ``"acceptance_rate"``
+        (``[n_kept]``: the accepted share of each kept transition) of the kept positions and ``"kinetic_temperature"``, the
+        mean of ``v^2`` over chains and coordinates of the final velocities (``T`` in law); with ``return_velocity`` the final
+        velocities come last.  The caller's ``x`` and ``velocity`` are never written.
+
+        Raises:
+            ValueError: ``thin < 1``, ``x`` and ``dim`` both ``None``, or a ``velocity`` whose shape differs from the state's.
+        """
+        if thin < 1:
+            raise ValueError("thin must be >= 1")
+        if reset_schedulers:
+            self.reset_schedulers()
+        x = self._init_state(x, dim, n_samples, generator)
+        if velocity is not None:
+            if tuple(velocity.shape) != tuple(x.shape):
+                raise ValueError(f"velocity must have the state's shape {tuple(x.shape)}, got {tuple(velocity.shape)}")
+            velocity = velocity.to(device=self.device, dtype=self.dtype)
+        route, spec = self._route(x, None)
+        if route == "fused":
+            state, v, traj, diag = self._sample_fused(x, velocity, spec, n_steps, thin, return_trajectory, return_diagnostics, generator)
+        else:
+            state, v, traj, diag = self._sample_eager(x, velocity, n_steps, thin, return_trajectory, return_diagnostics, generator)
+        out = (traj if return_trajectory else state,)
+        if return_diagnostics:
+            diag["kinetic_temperature"] = v.square().mean() if v.numel() else torch.full((), float("nan"), dtype=v.dtype, device=v.device)
+            out += (diag,)
+        if return_velocity:
+            out += (v,)
+        return out[0] if len(out) == 1 else out
+
+    # ---------------------------------------------------------------------------------
+    # route: torch ops
+    # ---------------------------------------------------------------------------------
+    # the two draws of the eager route, in one place each: a test replays one device's draws on another through them
+    def _draw_normal(self, shape, like: torch.Tensor, generator) -> torch.Tensor:
+        return torch.randn(shape, dtype=like.dtype, device=like.device, generator=generator)
+
+    def _draw_uniform(self, n: int, like: torch.Tensor, generator) -> torch.Tensor:
+        return torch.rand(n, dtype=like.dtype, device=like.device, generator=generator)
+
+    def _sample_eager(self, x, v, n_steps, thin, want_traj, want_diag, generator):
+        traj, diag = new_outputs(x, x.shape, n_steps // thin, want_traj, want_diag, acceptance=True)
+        energy = lambda x_: self._model_energy(x_, {})  # noqa: E731
+        clamped_energy = lambda x_: energy(x_).clamp_(min=-1e10, max=1e10)  # noqa: E731
+        kinetic = lambda v_: (0.5 * torch.sum(v_.flatten(1).square(), dim=-1)).clamp_(min=0.0, max=1e10)  # noqa: E731
+        force = lambda x_: (-self._model_gradient(x_, {})).clamp_(min=-1e6, max=1e6)  # noqa: E731
+        per_chain = lambda m: m.view(-1, *([1] * (x.ndim - 1)))  # noqa: E731
+        n, L = x.shape[0], self.n_leapfrog_steps
+        if v is None:
+            sqrt_temp = ghmc_constants(1.0, 1, self.friction, self.temperature, x.dtype)[2]
+            v = sqrt_temp * self._draw_normal(x.shape, x, generator)
+        keep = 0
+        with self.autocast_context():
+            for t in range(n_steps):
+                eps = self.get_scheduled_value("step_size")
+                c1, c2, _, beta = ghmc_constants(eps, L, self.friction, self.temperature, x.dtype)
+                xi = self._draw_normal(x.shape, x, generator)
+                u = self._draw_uniform(n, x, generator)
+                # every operation rounded on its own, in the order of the contract (include/ebm_hip.h)
+                v = c1 * v + c2 * xi  # O
+                h0 = clamped_energy(x) + kinetic(v)
+                eps_t = torch.full((), float(eps), dtype=x.dtype, device=x.device)
+                xp, vp = x, v
+                for _ in range(L):  # the safe-mode leapfrog step of integrators/symplectic.py, identity mass
+                    v_half = vp + 0.5 * eps_t * force(xp)
+                    xp = xp + eps_t * v_half
+                    vp = v_half + 0.5 * eps_t * force(xp)
+                    xp = xp.nan_to_num_(nan=0.0)
+                    vp = vp.nan_to_num_(nan=0.0)
+                h1 = clamped_energy(xp) + kinetic(vp)
+                accept_prob = torch.exp((beta * (h0 - h1)).clamp_(min=-50.0, max=50.0)).clamp_(max=1.0)
+                accepted = u < accept_prob
+                x = torch.where(per_chain(accepted), xp, x)
+                v = torch.where(per_chain(accepted), vp, -v)  # the flip
+                self.step_schedulers()
+                if (t + 1) % thin == 0:
+                    record_kept(x, keep, traj, diag, energy, accepted)
+                    keep += 1
+        if n_steps == 0:  # never the caller's tensors
+            x, v = x.clone(), v.clone()
+        return x, v, traj, diag
+
+    # ---------------------------------------------------------------------------------
+    # route: one launch of ebm_ghmc_chain_f32
+    # ---------------------------------------------------------------------------------
+    def _sample_fused(self, x, v, spec: FusedSpec, n_steps, thin, want_traj, want_diag, generator):
+        n, dim = x.shape
+        n_kept = n_steps // thin
+        state = _lib.dense_f32(x).clone()  # the kernel updates in place; never the caller's tensors
+        draw_v0 = v is None
+        vel = torch.empty_like(state) if draw_v0 else _lib.dense_f32(v).clone()
+        need_kept = (want_traj or want_diag) and n_kept > 0
+        traj = torch.empty(n, n_kept, dim, dtype=torch.float32, device=x.device) if (want_traj or need_kept) else None
+        mask = torch.empty(n_steps, n, dtype=torch.uint8, device=x.device) if (want_diag and n_kept > 0) else None
+        seed, step0 = _rng.reserve(generator, x.device, 2 * n_steps + 1)
+        stream = _lib.stream_handle(x.device)
+        spec_c = spec.to_c()
+        if n > 0 and n_steps > 0:
+            _lib.call(
+                "ebm_ghmc_chain_f32",
+                spec_c, _lib.ptr(state), _lib.ptr(vel), n, dim, n_steps, self.n_leapfrog_steps, self.get_scheduled_value("step_size"),
+                self.friction, self.temperature, int(draw_v0), thin, _lib.ptr(traj) if need_kept else None, _lib.ptr(mask), None, None,
+                seed, step0, stream,
+            )
+        elif draw_v0:  # no transition: the start velocities alone, the same field
+            if n > 0:
+                flat = torch.empty((n * dim + 3) // 4 * 4, dtype=torch.float32, device=x.device)
+                _lib.call("ebm_noise_fill_f32", _lib.ptr(flat), n * dim, _lib.NOISE_NORMAL, seed, step0, stream)
+                vel = ghmc_constants(1.0, 1, self.friction, self.temperature)[2] * flat[: n * dim].view(n, dim)
+        self.advance_schedulers(n_steps)
+        diag = None
+        if want_diag:
+            diag = new_outputs(state, state.shape, n_kept, False, True, acceptance=True)[1]
+            if n > 0 and n_kept > 0:
+                kept_statistics(spec_c, traj, diag, stream)
+                diag["acceptance_rate"].copy_(mask[thin - 1 :: thin][:n_kept].float().mean(dim=1))
+        return state, vel, (traj if want_traj else None), diag
