@@ -606,6 +606,60 @@ EBM_API int ebm_ghmc_chain_f32(const ebm_energy_t* energy, float* x, float* v, i
                                int32_t thin, float* traj, uint8_t* accept_mask, const float* noise, const float* u,
                                uint64_t seed, uint64_t offset, void* stream);
 
+/*
+ * Per-chain running moments of the two velocity-carrying samplers: k_steps transitions of the BAOAB walker of
+ * ebm_kinetic_chain_f32 (sampler = 0) or of the generalized-HMC walker of ebm_ghmc_chain_f32 (sampler = 1) per chain that
+ * keeps, beside position and velocity, the Welford pairs of ebm_chain_moments_f32 in registers, in ONE launch (an addition to
+ * ABI 9: nothing else moved).  The host forms split-R-hat, a between-sequence effective sample size and pooled moments from
+ * them (torchebm_amd/samplers/moments.py) without a trajectory.
+ *
+ * Counted states, accumulator, recip, mom, e_mom, traj, e_traj: exactly as in ebm_chain_moments_f32.  The first burn_in
+ * transitions are not counted; k_steps - burn_in == 2 h with h >= 2 is required; a counted state is the state AFTER the
+ * transition; per coordinate, per half and with c = 1 .. h
+ *     d = x - mean;   mean = mean + d * recip[c - 1];   M2 = M2 + d * (x - mean)
+ * in fp32, every operation rounded on its own, recip[c - 1] = (float)(1.0 / c).
+ *
+ * BAOAB (sampler = 0; step = h).  The constants hh, c1, c2, sqrt_temp and the recurrence B A O A (g) B of
+ * ebm_kinetic_chain_f32, operation for operation: the raw unclamped gradient, the kicks not merged, the start's gradient from
+ * one evaluation in front of the loop.  z is the normal field at Philox step offset + 1 + s, element chain * dim + col, or
+ * the injected noise[k_steps, n_chains, dim]; draw_v0 != 0 starts from sqrt_temp * z0, z0 at step offset.  A call owns the
+ * steps offset .. offset + k_steps: the final x and v equal ebm_kinetic_chain_f32's on the same draws.  n_leapfrog, u,
+ * accept_mask and accept_count are ignored.
+ *   e_mom   NULL, or float[4][n_chains]: the energy of the post-step position, returned by the one evaluation inside the
+ *           step together with the gradient -- that position is the counted state, so no evaluation is added.  With
+ *           e_mom == NULL the kernel is another instantiation that carries no group reduction (and writes no e_traj).
+ *   v2_mom  NULL, or float[2][n_chains][dim]: the running mean of v^2 per coordinate and half, v the velocity at the END of
+ *           the step (behind the closing B):   m = m + (v * v - m) * recip[c - 1],   each operation rounded on its own.  On a
+ *           quadratic energy E'' = k its expectation is T (1 - h^2 k / 4): the step-size error read off the run.
+ *   v_traj  NULL, or float[n_chains][2 h][dim]: those velocities.  For tests and small runs, as traj and e_traj.
+ *
+ * GHMC (sampler = 1; step = eps, n_leapfrog = L >= 1).  The constants c1, c2, sqrt_temp, beta and the transition of
+ * ebm_ghmc_chain_f32, operation for operation: the O refresh, the uniform drawn in front of the trajectory, n_leapfrog
+ * safe-mode leapfrog steps (identity mass, carried energy and force, the pseudo-transition for the start),
+ * accepted iff u < min(1, exp(clamp(beta (H0 - H1), +-50))), the velocity flipped on a reject.  z_t at step offset + 1 + 2 t,
+ * the uniform at offset + 2 + 2 t, element chain; noise[k_steps, n_chains, dim] / u[k_steps, n_chains] in their place, either
+ * without the other; draw_v0 as above.  A call owns the steps offset .. offset + 2 k_steps: the final x, v and the accept mask
+ * equal ebm_ghmc_chain_f32's on the same draws.  Counted: the held position and the carried energy; a reject counts the held
+ * state again; no evaluation is added.  accept_mask: NULL, or uint8[k_steps][n_chains]; accept_count: NULL, or device
+ * uint32[k_steps] the call ADDS to (one atomic per wave and transition).  v2_mom and v_traj must be NULL: the velocity law is
+ * exact under the Metropolis correction and carries no information.
+ *
+ * Outputs.  x and v are updated in place and stored once, mom / e_mom / v2_mom once at the end.  Slots of a lane that hold no
+ * column never reach memory.
+ *
+ * Limits: every analytic energy except EBM_ENERGY_MLP (EBM_EKIND); 1 <= dim <= 256, one vector per lane (EBM_EDIM, in front of
+ * any device access); constants only: no clamp, no tables, no mass matrix; 64-bit row indices.  EBM_EINVAL with no buffer
+ * touched: a NULL energy, x, v, mom or recip; an unknown sampler; burn_in < 0 or k_steps - burn_in not 2 h with h >= 2; step,
+ * gamma or temperature not positive, or NaN (all finite for BAOAB; gamma = +inf, the full refresh, allowed for GHMC);
+ * n_leapfrog < 1, a non-NULL v2_mom or a non-NULL v_traj for GHMC.  An empty call (n_chains == 0) returns 0 behind these checks.
+ */
+EBM_API int ebm_kinetic_moments_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim,
+                                    int32_t sampler, int32_t k_steps, int32_t burn_in, int32_t n_leapfrog, double step,
+                                    double gamma, double temperature, int32_t draw_v0, const float* recip, float* mom,
+                                    float* e_mom, float* v2_mom, float* traj, float* e_traj, float* v_traj,
+                                    uint8_t* accept_mask, uint32_t* accept_count, const float* noise, const float* u,
+                                    uint64_t seed, uint64_t offset, void* stream);
+
 /* The accept step with the RNG coordinates in DEVICE memory (rng_state = {seed, step}; the uniforms
  * are drawn at step rng_state[1] + step_delta): the graph-capturable form, see
  * ebm_langevin_step_dev_f32.  No injected-uniform form. */

@@ -581,6 +581,55 @@ int ebm_ghmc_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n
   return ghmc_chain_launch(q, (hipStream_t)stream);
 }
 
+int ebm_kinetic_moments_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t sampler,
+                            int32_t k_steps, int32_t burn_in, int32_t n_leapfrog, double step, double gamma, double temperature,
+                            int32_t draw_v0, const float* recip, float* mom, float* e_mom, float* v2_mom, float* traj,
+                            float* e_traj, float* v_traj, uint8_t* accept_mask, uint32_t* accept_count, const float* noise,
+                            const float* u, uint64_t seed, uint64_t offset, void* stream) {
+  const char* who = "ebm_kinetic_moments_f32";
+  if (energy && energy->kind == EBM_ENERGY_MLP)
+    return fail(EBM_EKIND, "%s: the MLP energy has no running-moments kernel (the samplers' eager route takes it)", who);
+  if (int r = check_energy(energy, dim, who)) return r;
+  if (int r = kinetic_moments_check_geometry(dim)) return r;  // (in front of check_state: dim < 1 is EBM_EDIM here, as dim > 256 is)
+  if (int r = check_state(x, n_chains, dim, who)) return r;
+  if (!v) return fail(EBM_EINVAL, "%s: velocity pointer is NULL", who);
+  if (sampler != 0 && sampler != 1) return fail(EBM_EINVAL, "%s: sampler=%d (0 = BAOAB, 1 = GHMC)", who, sampler);
+  const bool ghmc = sampler == 1;
+  if (k_steps < 0 || burn_in < 0 || burn_in > k_steps || ((k_steps - burn_in) & 1) || (k_steps - burn_in) / 2 < 2)
+    return fail(EBM_EINVAL, "%s: k_steps=%d burn_in=%d (k_steps - burn_in must be 2 h with h >= 2)", who, k_steps, burn_in);
+  // (GHMC: gamma = +inf is allowed, a full refresh)
+  if (!(step > 0.0) || !(gamma > 0.0) || !(temperature > 0.0) || !std::isfinite(step) || !std::isfinite(temperature) ||
+      (!ghmc && !std::isfinite(gamma)))
+    return fail(EBM_EINVAL, "%s: step=%g gamma=%g temperature=%g (all must be positive; finite, but for GHMC's gamma)", who, step,
+                gamma, temperature);
+  if (ghmc && n_leapfrog < 1) return fail(EBM_EINVAL, "%s: n_leapfrog=%d", who, n_leapfrog);
+  if (ghmc && (v2_mom || v_traj)) return fail(EBM_EINVAL, "%s: v2_mom / v_traj are BAOAB outputs (sampler = 0)", who);
+  if (!recip || !mom) return fail(EBM_EINVAL, "%s: recip / mom is NULL", who);
+  if (n_chains == 0) return 0;
+  if (!aligned16(v) || !aligned16(mom) || (v2_mom && !aligned16(v2_mom)) || (traj && !aligned16(traj)) ||
+      (v_traj && !aligned16(v_traj)) || (noise && !aligned16(noise)))
+    return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  // the constants of either walker, as its chain entry forms them: in double, each rounded once
+  const float sqrt_temp = (float)sqrt(temperature);
+  float hh = 0.0f, eps = 0.0f, c1, c2, beta = 0.0f;
+  if (ghmc) {
+    const double span = gamma * step * (double)n_leapfrog;
+    eps = (float)step;
+    c1 = std::isinf(gamma) ? 0.0f : (float)exp(-span);
+    c2 = std::isinf(gamma) ? sqrt_temp : (float)sqrt(temperature * (-expm1(-2.0 * span)));
+    beta = (float)(1.0 / temperature);
+  } else {
+    hh = (float)(0.5 * step);
+    c1 = (float)exp(-gamma * step);
+    c2 = (float)sqrt(temperature * (-expm1(-2.0 * gamma * step)));
+  }
+  const KineticMomentsChainReq q{*energy, x, v, n_chains, dim, ghmc, k_steps, burn_in, n_leapfrog, hh, eps, c1, c2, sqrt_temp,
+                                 beta, draw_v0 != 0, recip, mom, e_mom, ghmc ? nullptr : v2_mom, traj, e_traj,
+                                 ghmc ? nullptr : v_traj, ghmc ? accept_mask : nullptr, ghmc ? accept_count : nullptr, noise,
+                                 ghmc ? u : nullptr, seed, offset};
+  return kinetic_moments_chain_launch(q, (hipStream_t)stream);
+}
+
 int ebm_leapfrog_kick_drift_f32(const float* x, const float* p, const float* force, float* x_new,
                                 float* p_half, int64_t n_chains, int32_t dim, float eps,
                                 int32_t mass_kind, double mass_scalar, const float* mass_diag,

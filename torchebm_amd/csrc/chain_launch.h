@@ -179,6 +179,35 @@ struct GhmcChainReq {
   int32_t n_kept() const { return n_mh / thin; }
 };
 
+struct KineticMomentsChainReq {
+  const ebm_energy_t& e;
+  float* x;                // [n_chains, dim], in/out
+  float* v;                // [n_chains, dim]: in/out, output only with draw_v0
+  int64_t n_chains;
+  int32_t dim;
+  bool ghmc;               // the sampler: false = BAOAB, true = generalized HMC
+  int32_t k_steps, burn_in, n_leapfrog;
+  // BAOAB: h / 2, exp(-gamma h), sqrt(T (1 - exp(-2 gamma h))); GHMC: eps, exp(-gamma eps L), sqrt(T (1 - exp(-2 gamma eps L))),
+  // 1 / T; both: sqrt(T) -- formed in double, rounded once, as the two chain entries form them
+  float hh, eps, c1, c2, sqrt_temp, beta;
+  bool draw_v0;
+  const float* recip;      // device [half_len()]
+  float* mom;              // [4, n_chains, dim]
+  float* e_mom;            // [4, n_chains] or null
+  float* v2_mom;           // [2, n_chains, dim] or null (BAOAB)
+  float* traj;             // [n_chains, 2 half_len(), dim] or null
+  float* e_traj;           // [n_chains, 2 half_len()] or null
+  float* v_traj;           // [n_chains, 2 half_len(), dim] or null (BAOAB)
+  uint8_t* accept_mask;    // [k_steps, n_chains] or null (GHMC)
+  uint32_t* accept_count;  // [k_steps] or null (GHMC)
+  const float* noise;      // [k_steps, n_chains, dim] or null
+  const float* u;          // [k_steps, n_chains] or null (GHMC)
+  uint64_t seed, offset;
+
+  RngKey key() const { return RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)}; }
+  int32_t half_len() const { return (k_steps - burn_in) / 2; }
+};
+
 // The fields the row-major Langevin argument structs share (GaussArgs, BigArgs, RowChainArgs, WideArgs).
 template <class Args>
 inline void fill_langevin(Args& a, const LangevinChainReq& q) {
@@ -309,5 +338,11 @@ int kinetic_check_geometry(int32_t dim);  // 0, or the refusal (dim > 256)
 // ---------------------------------------------------------------------------------
 int ghmc_chain_launch(const GhmcChainReq&, hipStream_t);
 int ghmc_check_geometry(int32_t dim);  // 0, or the refusal (dim > 256)
+
+// ---------------------------------------------------------------------------------
+// Running moments of the two (kinetic_moments.hip: the BAOAB or the GHMC walker with Welford pairs beside position and velocity)
+// ---------------------------------------------------------------------------------
+int kinetic_moments_chain_launch(const KineticMomentsChainReq&, hipStream_t);
+int kinetic_moments_check_geometry(int32_t dim);  // 0, or the refusal (dim outside 1 .. 256)
 
 }  // namespace ebm

@@ -1,0 +1,3 @@
+// The generalized-HMC half of the kinetic running-moments family: see kinetic_moments_unit.hip.
+#define EBM_KINETIC_MOMENTS_GHMC 1
+#include "kinetic_moments_unit.hip"

@@ -164,6 +164,35 @@ class GeneralizedHMC(BaseSampler):
             out += (v,)
         return out[0] if len(out) == 1 else out
 
+    def sample_moments(
+        self,
+        x: Optional[torch.Tensor] = None,
+        dim: Optional[Union[int, Tuple[int, ...]]] = None,
+        n_steps: int = 100,
+        n_samples: int = 1,
+        burn_in: int = 0,
+        energy: bool = False,
+        *,
+        velocity: Optional[torch.Tensor] = None,
+        return_velocity: bool = False,
+        generator: Optional[torch.Generator] = None,
+    ):
+        """Run ``n_steps`` transitions and keep per-chain running moments of the held positions after the first ``burn_in``
+        (with ``energy`` of their energies too; a reject counts the held state again) -- no trajectory is written.
+
+        Returns ``(x_final, ChainMoments)``, with ``return_velocity`` ``(x_final, ChainMoments, v_final)``.  The moments
+        carry ``rhat``, ``ess``, ``mean``, ``var`` and ``acceptance_rate`` (``[n_steps]``).  When ``n_steps - burn_in`` is
+        odd one more transition is burnt.  On the fused route (see the module docstring) the call is ONE launch of
+        ``ebm_kinetic_moments_f32`` and ``x_final``, ``v_final`` are ``sample(return_velocity=True)``'s for the same
+        generator state.  The caller's ``x`` and ``velocity`` are never written.
+
+        Raises:
+            ValueError: fewer than 4 counted steps, ``burn_in`` outside ``0 .. n_steps``, a ``velocity`` of another shape.
+        """
+        from .kinetic_moments import sample_moments
+
+        return sample_moments(self, True, x, dim, n_steps, n_samples, burn_in, energy, velocity, return_velocity, generator)
+
     # ---------------------------------------------------------------------------------
     # route: torch ops
     # ---------------------------------------------------------------------------------

@@ -77,7 +77,8 @@ class UnderdampedLangevin(BaseSampler):
     # ---------------------------------------------------------------------------------
     # routing: decided here and nowhere else
     # ---------------------------------------------------------------------------------
-    def _route(self, x: torch.Tensor) -> Tuple[str, Optional[FusedSpec]]:
+    def _route(self, x: torch.Tensor, model_kwargs=None) -> Tuple[str, Optional[FusedSpec]]:
+        # (model_kwargs: unused -- the signature of the other samplers' _route, which the tests' CPU stand-in replaces)
         if not x.is_cuda or x.dtype != torch.float32 or x.ndim != 2:
             return "eager", None
         if not self.schedulers["step_size"].is_constant():
@@ -132,7 +133,7 @@ class UnderdampedLangevin(BaseSampler):
             if tuple(velocity.shape) != tuple(x.shape):
                 raise ValueError(f"velocity must have the state's shape {tuple(x.shape)}, got {tuple(velocity.shape)}")
             velocity = velocity.to(device=self.device, dtype=self.dtype)
-        route, spec = self._route(x)
+        route, spec = self._route(x, None)
         if route == "fused":
             state, v, traj, diag = self._sample_fused(x, velocity, spec, n_steps, thin, return_trajectory, return_diagnostics, generator)
         else:
@@ -144,6 +145,36 @@ class UnderdampedLangevin(BaseSampler):
         if return_velocity:
             out += (v,)
         return out[0] if len(out) == 1 else out
+
+    def sample_moments(
+        self,
+        x: Optional[torch.Tensor] = None,
+        dim: Optional[Union[int, Tuple[int, ...]]] = None,
+        n_steps: int = 100,
+        n_samples: int = 1,
+        burn_in: int = 0,
+        energy: bool = False,
+        *,
+        velocity: Optional[torch.Tensor] = None,
+        return_velocity: bool = False,
+        generator: Optional[torch.Generator] = None,
+    ):
+        """Run ``n_steps`` BAOAB steps and keep per-chain running moments of the positions after the first ``burn_in``
+        (with ``energy`` of their energies too) and the running mean of ``v^2`` -- no trajectory is written.
+
+        Returns ``(x_final, ChainMoments)``, with ``return_velocity`` ``(x_final, ChainMoments, v_final)``.  The moments
+        carry ``rhat``, ``ess``, ``mean``, ``var`` and ``kinetic_temperature``, the time- and chain-averaged ``v^2`` per
+        coordinate: an estimate of ``T (1 - h^2 E'' / 4)``.  When ``n_steps - burn_in`` is odd one more step is burnt.  On
+        the fused route (see the module docstring) the call is ONE launch of ``ebm_kinetic_moments_f32`` and ``x_final``,
+        ``v_final`` are ``sample(return_velocity=True)``'s for the same generator state.  The caller's ``x`` and
+        ``velocity`` are never written.
+
+        Raises:
+            ValueError: fewer than 4 counted steps, ``burn_in`` outside ``0 .. n_steps``, a ``velocity`` of another shape.
+        """
+        from .kinetic_moments import sample_moments
+
+        return sample_moments(self, False, x, dim, n_steps, n_samples, burn_in, energy, velocity, return_velocity, generator)
 
     # ---------------------------------------------------------------------------------
     # route: torch ops

@@ -1,0 +1,109 @@
+r"""Running moments of the two velocity-carrying samplers: what ``UnderdampedLangevin.sample_moments`` and
+``GeneralizedHMC.sample_moments`` run.
+
+The statistics are those of :mod:`torchebm_amd.samplers.moments` -- a Welford pair per chain, coordinate and half of the
+counted steps, fp32, beside the state; :class:`ChainMoments` forms split-:math:`\hat R`, the between-sequence ESS and the
+pooled moments -- plus, under BAOAB, the running mean of ``v^2`` per coordinate and half (``ChainMoments.velocity_sq_mean``,
+``kinetic_temperature``): on a quadratic energy ``E'' = k`` its expectation is ``T (1 - h^2 k / 4)``, the step-size error read
+off the run.  Generalized HMC keeps none: its velocity law is exact and carries no information.
+
+Two execution routes, chosen once per call:
+
+``fused``  what the sampler's own ``_route`` calls fused, with ``dim >= 1``: ONE launch of ``ebm_kinetic_moments_f32``
+           (include/ebm_hip.h states the algorithm exactly; docs/design/kinetic_moments.md the kernels).  ``_rng.reserve``
+           takes ``k + 1`` Philox steps for BAOAB and ``2 k + 1`` for GHMC, the coordinates ``sample()`` draws at: the final
+           ``x`` and ``v`` are ``sample(return_velocity=True)``'s bit for bit.  GHMC's ``acceptance_rate`` is summed from the
+           entry's accept mask while that stays under ``MASK_MAX_BYTES``, from its per-transition counters beyond.
+``eager``  anything else, CPU included: the sampler's own ``sample(n_steps=1, velocity=v, return_velocity=True)`` per
+           transition around :class:`RunningMoments`, with the same reciprocal table; the ``v^2`` mean by the same recurrence
+           in the state's dtype.
+
+A fused-eligible call never falls back to eager: a missing library or a failing launch raises.
+"""
+
+from __future__ import annotations
+
+import torch
+
+from .. import _lib, _rng
+from .moments import ChainMoments, RunningMoments, recip_table, split_counted
+
+SAMPLER_BAOAB, SAMPLER_GHMC = 0, 1
+MASK_MAX_BYTES = 1 << 28  # the largest accept mask [k, n] the fused GHMC route allocates; beyond it the entry's counters are used
+
+
+@torch.no_grad()
+def sample_moments(sampler, ghmc: bool, x, dim, n_steps, n_samples, burn_in, energy, velocity, return_velocity, generator):
+    burn_in, h = split_counted(n_steps, burn_in)
+    sampler.reset_schedulers()
+    x = sampler._init_state(x, dim, n_samples, generator)
+    if velocity is not None:
+        if tuple(velocity.shape) != tuple(x.shape):
+            raise ValueError(f"velocity must have the state's shape {tuple(x.shape)}, got {tuple(velocity.shape)}")
+        velocity = velocity.to(device=sampler.device, dtype=sampler.dtype)
+    route, spec = sampler._route(x, None)
+    if route == "fused" and x.shape[0] > 0 and x.shape[1] >= 1:
+        state, v, res = _fused(sampler, ghmc, spec, x, velocity, int(n_steps), burn_in, h, bool(energy), generator)
+    else:
+        state, v, res = _eager(sampler, ghmc, x, velocity, int(n_steps), burn_in, h, bool(energy), generator)
+    return (state, res, v) if return_velocity else (state, res)
+
+
+def _eager(sampler, ghmc, x, v, k, burn_in, h, energy, generator):
+    acc = RunningMoments(h, with_energy=energy)
+    v2 = None if ghmc else torch.zeros((2, *x.shape), dtype=x.dtype, device=x.device)
+    rates = []
+    for s in range(k):
+        out = sampler.sample(x=x, n_steps=1, return_diagnostics=ghmc, reset_schedulers=False, velocity=v, return_velocity=True,
+                             generator=generator)
+        if ghmc:
+            x, diag, v = out
+            rates.append(diag["acceptance_rate"][0])
+        else:
+            x, v = out
+        if s >= burn_in:
+            half, c = divmod(s - burn_in, h)
+            acc.add(x, sampler._model_energy(x, {}) if energy else None)
+            if v2 is not None:  # m = m + (v v - m) recip[c - 1], every operation rounded on its own
+                rc = acc.recip[c].to(dtype=x.dtype).item()
+                v2[half] = v2[half] + (v * v - v2[half]) * rc
+    rate = torch.stack(rates).to(torch.float32) if ghmc else None
+    res = ChainMoments(acc.mean, acc.m2, h, acc.e_mean, acc.e_m2, rate, v2)
+    return x, v, res
+
+
+def _fused(sampler, ghmc, spec, x, v, k, burn_in, h, energy, generator):
+    n, dim = x.shape
+    dev = x.device
+    state = _lib.dense_f32(x).clone()  # the kernel updates in place; never the caller's tensors
+    draw_v0 = v is None
+    vel = torch.empty_like(state) if draw_v0 else _lib.dense_f32(v).clone()
+    recip = recip_table(h).to(dev)
+    mom = torch.empty(4, n, dim, dtype=torch.float32, device=dev)
+    e_mom = torch.empty(4, n, dtype=torch.float32, device=dev) if energy else None
+    v2 = None if ghmc else torch.empty(2, n, dim, dtype=torch.float32, device=dev)
+    # GHMC's acceptance per transition: from the accept mask while it is small (a byte per chain and transition), else from the
+    # entry's counters -- one atomic per wave on k shared addresses, which at 2^16 x 32, k = 200 costs 3.6 ms of 4.6
+    # (docs/design/kinetic_moments.md)
+    mask = counts = None
+    if ghmc and k * n <= MASK_MAX_BYTES:
+        mask = torch.empty(k, n, dtype=torch.uint8, device=dev)
+    elif ghmc:
+        counts = torch.zeros(k, dtype=torch.int32, device=dev)  # (uint32 counters in an int32 tensor)
+    seed, step0 = _rng.reserve(generator, dev, (2 * k if ghmc else k) + 1)
+    _lib.call(
+        "ebm_kinetic_moments_f32",
+        spec.to_c(), _lib.ptr(state), _lib.ptr(vel), n, dim, SAMPLER_GHMC if ghmc else SAMPLER_BAOAB, k, burn_in,
+        int(sampler.n_leapfrog_steps) if ghmc else 0, float(sampler.get_scheduled_value("step_size")), sampler.friction,
+        sampler.temperature, int(draw_v0), _lib.ptr(recip), _lib.ptr(mom), _lib.ptr(e_mom), _lib.ptr(v2), None, None, None,
+        _lib.ptr(mask), _lib.ptr(counts), None, None, seed, step0, _lib.stream_handle(dev),
+    )
+    sampler.advance_schedulers(k)
+    rate = None
+    if ghmc:
+        accepted = mask.sum(dim=1, dtype=torch.int64) if mask is not None else counts.to(torch.int64) & 0xFFFFFFFF
+        rate = (accepted.to(torch.float64) / n).to(torch.float32)
+    res = ChainMoments(torch.stack((mom[0], mom[2])), torch.stack((mom[1], mom[3])), h,
+                       torch.stack((e_mom[0], e_mom[2])) if energy else None,
+                       torch.stack((e_mom[1], e_mom[3])) if energy else None, rate, v2)
+    return state, vel, res

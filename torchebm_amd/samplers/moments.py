@@ -101,7 +101,8 @@ class ChainMoments:
 
     Holds ``chain_mean`` and ``chain_m2`` of shape ``[2, n, dim]`` (half, chain, coordinate; ``m2`` is the sum of squared
     deviations from the half's mean), when the energy was requested ``energy_mean`` and ``energy_m2`` of shape ``[2, n]``,
-    ``half_len`` and, for HMC, ``acceptance_rate`` (``[n_steps]``, accepted / proposed per transition).
+    ``half_len``, for HMC and generalized HMC ``acceptance_rate`` (``[n_steps]``, accepted / proposed per transition) and, for
+    ``UnderdampedLangevin``, ``velocity_sq_mean`` of shape ``[2, n, dim]``: the time average of ``v^2`` over either half.
 
     Everything below is computed once, in float64, from ``M = 2 n`` sequences of length ``l = half_len`` (the half-chains).
     Chains with any non-finite moment are left out and counted in ``n_nonfinite``.
@@ -116,13 +117,16 @@ class ChainMoments:
       for the many-chain regime this package runs in, and for ``l`` well above the autocorrelation time -- shorter halves
       are still correlated with each other's neighbours inside a chain and the figure is then optimistic.
     * ``mean``, ``var``: the pooled posterior mean and (unbiased) variance per coordinate over all counted states.
+    * ``kinetic_temperature``: the mean of ``velocity_sq_mean`` over halves and chains, per coordinate; ``None`` without it.
     """
 
-    def __init__(self, chain_mean, chain_m2, half_len, energy_mean=None, energy_m2=None, acceptance_rate=None):
+    def __init__(self, chain_mean, chain_m2, half_len, energy_mean=None, energy_m2=None, acceptance_rate=None,
+                 velocity_sq_mean=None):
         self.chain_mean, self.chain_m2 = chain_mean, chain_m2
         self.energy_mean, self.energy_m2 = energy_mean, energy_m2
         self.half_len = int(half_len)
         self.acceptance_rate = acceptance_rate
+        self.velocity_sq_mean = velocity_sq_mean
         self._stats = None
 
     @staticmethod
@@ -153,18 +157,32 @@ class ChainMoments:
         if have_e:
             e_mean, e_m2 = self.energy_mean.detach().to(torch.float64), self.energy_m2.detach().to(torch.float64)
             good &= torch.isfinite(e_mean).all(dim=0) & torch.isfinite(e_m2).all(dim=0)
+        have_v2 = self.velocity_sq_mean is not None
+        if have_v2:
+            v2 = self.velocity_sq_mean.detach().to(torch.float64).reshape(2, n, -1)
+            good &= torch.isfinite(v2).all(dim=2).all(dim=0)
         shape = tuple(self.chain_mean.shape[2:])
         seq = lambda t: t[:, good].reshape(-1, *t.shape[2:])  # noqa: E731  ([2, n', ...] -> [2 n', ...])
         st = {k: v.reshape(shape) for k, v in self._figures(seq(mean), seq(m2), self.half_len).items()}
         if have_e:
             st.update({"energy_" + k: v for k, v in self._figures(seq(e_mean), seq(e_m2), self.half_len).items()})
+        if have_v2:
+            # both halves hold half_len steps: the mean over halves and chains is the mean over all counted velocities
+            st["kinetic_temperature"] = v2[:, good].mean(dim=(0, 1)).reshape(shape)
         st["n_nonfinite"] = int(n - int(good.sum()))
         st["n_sequences"] = 2 * int(good.sum())
         self._stats = st
         return st
 
+    @property
+    def kinetic_temperature(self) -> Optional[torch.Tensor]:
+        """The time- and chain-averaged ``v^2`` per coordinate (float64, over the chains with finite moments), or ``None``
+        when the run kept no ``velocity_sq_mean``.  Under BAOAB on a quadratic energy it estimates ``T (1 - h^2 E'' / 4)``."""
+        return self._compute().get("kinetic_temperature")
+
     def __getattr__(self, name):
-        if name.startswith("_") or name in ("chain_mean", "chain_m2", "energy_mean", "energy_m2", "half_len", "acceptance_rate"):
+        if name.startswith("_") or name in ("chain_mean", "chain_m2", "energy_mean", "energy_m2", "half_len", "acceptance_rate",
+                                            "velocity_sq_mean"):
             raise AttributeError(name)
         st = self._compute()
         if name in st:
