@@ -559,6 +559,42 @@ EBM_API int ebm_kinetic_chain_f32(const ebm_energy_t* energy, float* x, float* v
                                   float* traj, const float* noise, uint64_t seed, uint64_t offset, void* stream);
 
 /*
+ * Underdamped Langevin (BAOAB) on the MLP energy: the walk of ebm_kinetic_chain_f32 above -- the same parameter list, the same
+ * constants formed in double and rounded once, the same Philox coordinates -- with the matrix-core evaluation of
+ * ebm_hmc_chain_f32 / ebm_ais_mlp_chain_f32 inside the step loop, in ONE launch (an addition to ABI 9: nothing else moved;
+ * ebm_kinetic_chain_f32 still refuses the MLP).  One wave walks 32 chains; only the gradient is evaluated, never the energy.
+ *
+ * Recurrence.  The contract above restated for a loop with ONE evaluation site: k_steps + 1 evaluations i = 0 .. k_steps, every
+ * product and sum rounded on its own, the raw gradient unclamped (a NaN stays in its chain):
+ *     g = dE/dx(x)
+ *     if i > 0:  v = v - hh * g             (the closing B of step i - 1; then x goes to traj if i % thin == 0)
+ *     if i == k_steps: stop
+ *     v = v - hh * g                        (the opening B: never merged with the closing one)
+ *     x = x + hh * v                        (A)
+ *     v = c1 * v + c2 * z_i                 (O)
+ *     x = x + hh * v                        (A)
+ * z_i is the normal field at Philox step offset + 1 + i, element chain * dim + col -- or the injected noise[k_steps, n_chains,
+ * dim].  draw_v0 != 0: v is output only and starts as sqrt_temp * z, z the field at step offset; draw_v0 == 0: v is read.  A
+ * call owns the steps offset .. offset + k_steps.  (k1, offset) then (k2, offset + k1) with draw_v0 = 0 equals one call of
+ * k1 + k2 bit for bit: the evaluation the second call starts with is the one the first call's last closing B used.
+ *
+ * Outputs.  x and v are updated in place and stored once; traj: NULL, or float[n_chains][k_steps / thin][dim].  Columns past
+ * dim never reach memory; 64-bit row indices.
+ *
+ * The evaluation is three-way split bf16 (or exact-f32 MFMA) arithmetic with fp32 accumulation: fp32 accuracy, not autograd's
+ * rounding.
+ *
+ * Refusals, all in front of any device access and of the early return for n_chains == 0: a NULL energy, x or v, k_steps < 1,
+ * thin < 1, h, gamma or temperature not positive and finite (EBM_EINVAL); a kind other than EBM_ENERGY_MLP (EBM_EKIND); a
+ * hidden width (energy->n_comp) other than 64 / 128 or dim outside 1 .. 128 (EBM_EDIM).  No H = 256, no pre-split W1 image
+ * (energy->aux is ignored), no clamp, no tables, no mass matrix, no diagnostics records.
+ */
+EBM_API int ebm_kinetic_mlp_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim,
+                                      int32_t k_steps, double h, double gamma, double temperature, int32_t draw_v0,
+                                      int32_t thin, float* traj, const float* noise, uint64_t seed, uint64_t offset,
+                                      void* stream);
+
+/*
  * Generalized HMC (Horowitz 1991; Metropolis-adjusted kinetic Langevin): n_mh transitions of a walker per chain that carries a
  * velocity beside its position, in ONE launch (an addition to ABI 9: nothing else moved).  Each transition refreshes the
  * velocity partially, runs a short Metropolis-corrected leapfrog trajectory and flips the velocity on a reject: exp(-E / T) is

@@ -525,6 +525,17 @@ int ebm_chain_moments_f32(const ebm_energy_t* energy, float* x, int64_t n_chains
   return moments_chain_launch(q, (hipStream_t)stream);
 }
 
+// The request of both underdamped-Langevin entries: the constants of the splitting, formed in double, each rounded once
+static KineticChainReq kinetic_request(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t k_steps,
+                                       double h, double gamma, double temperature, int32_t draw_v0, int32_t thin, float* traj,
+                                       const float* noise, uint64_t seed, uint64_t offset) {
+  const float hh = (float)(0.5 * h);
+  const float c1 = (float)exp(-gamma * h);
+  const float c2 = (float)sqrt(temperature * (-expm1(-2.0 * gamma * h)));
+  const float sqrt_temp = (float)sqrt(temperature);
+  return KineticChainReq{*energy, x, v, n_chains, dim, k_steps, hh, c1, c2, sqrt_temp, draw_v0 != 0, thin, traj, noise, seed, offset};
+}
+
 int ebm_kinetic_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t k_steps,
                           double h, double gamma, double temperature, int32_t draw_v0, int32_t thin, float* traj,
                           const float* noise, uint64_t seed, uint64_t offset, void* stream) {
@@ -541,13 +552,32 @@ int ebm_kinetic_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_
   if (n_chains == 0) return 0;
   if (!aligned16(v) || (traj && !aligned16(traj)) || (noise && !aligned16(noise)))
     return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
-  // the constants of the splitting: formed in double, each rounded once
-  const float hh = (float)(0.5 * h);
-  const float c1 = (float)exp(-gamma * h);
-  const float c2 = (float)sqrt(temperature * (-expm1(-2.0 * gamma * h)));
-  const float sqrt_temp = (float)sqrt(temperature);
-  const KineticChainReq q{*energy, x, v, n_chains, dim, k_steps, hh, c1, c2, sqrt_temp, draw_v0 != 0, thin, traj, noise, seed, offset};
-  return kinetic_chain_launch(q, (hipStream_t)stream);
+  return kinetic_chain_launch(kinetic_request(energy, x, v, n_chains, dim, k_steps, h, gamma, temperature, draw_v0, thin, traj, noise,
+                                              seed, offset),
+                              (hipStream_t)stream);
+}
+
+int ebm_kinetic_mlp_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t k_steps,
+                              double h, double gamma, double temperature, int32_t draw_v0, int32_t thin, float* traj,
+                              const float* noise, uint64_t seed, uint64_t offset, void* stream) {
+  const char* who = "ebm_kinetic_mlp_chain_f32";
+  if (int r = check_energy(energy, dim, who)) return r;
+  if (energy->kind != EBM_ENERGY_MLP)
+    return fail(EBM_EKIND, "%s: this entry walks the MLP energy only (ebm_kinetic_chain_f32 takes the analytic kinds)", who);
+  // (the dim range is kinetic_mlp_check_shape's to refuse)
+  if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
+  if (!v) return fail(EBM_EINVAL, "%s: velocity pointer is NULL", who);
+  if (n_chains < 0) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d]", who, (long long)n_chains, dim);
+  if (k_steps < 1 || thin < 1) return fail(EBM_EINVAL, "%s: k_steps=%d thin=%d (both must be >= 1)", who, k_steps, thin);
+  if (!(h > 0.0) || !(gamma > 0.0) || !(temperature > 0.0) || !std::isfinite(h) || !std::isfinite(gamma) || !std::isfinite(temperature))
+    return fail(EBM_EINVAL, "%s: h=%g gamma=%g temperature=%g (all must be positive and finite)", who, h, gamma, temperature);
+  if (int r = kinetic_mlp_check_shape(energy->n_comp, dim)) return r;
+  if (n_chains == 0) return 0;
+  if (!aligned16(x) || !aligned16(v) || (traj && !aligned16(traj)) || (noise && !aligned16(noise)))
+    return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  return kinetic_mlp_chain_launch(kinetic_request(energy, x, v, n_chains, dim, k_steps, h, gamma, temperature, draw_v0, thin, traj,
+                                                  noise, seed, offset),
+                                  (hipStream_t)stream);
 }
 
 int ebm_ghmc_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t n_mh,

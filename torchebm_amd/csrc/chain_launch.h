@@ -332,6 +332,9 @@ int moments_check_geometry(int32_t dim);  // 0, or the refusal (dim > 256)
 // ---------------------------------------------------------------------------------
 int kinetic_chain_launch(const KineticChainReq&, hipStream_t);
 int kinetic_check_geometry(int32_t dim);  // 0, or the refusal (dim > 256)
+// ... on the MLP energy (mlp_wide_kinetic.hip: the same request; 32 chains per wave around the matrix-core evaluation, k_steps + 1 of them per call)
+int kinetic_mlp_chain_launch(const KineticChainReq&, hipStream_t);
+int kinetic_mlp_check_shape(int32_t hidden, int32_t dim);  // 0, or the refusal (hidden width not 64 / 128, dim outside 1 .. 128)
 
 // ---------------------------------------------------------------------------------
 // Generalized HMC (ghmc.hip: the kinetic walker with a partial momentum refresh, a Metropolis-corrected trajectory and the flip)

@@ -31,7 +31,7 @@ A fused-eligible call never falls back to eager: a missing library or a failing 
 from __future__ import annotations
 
 import math
-from typing import Optional, Tuple, Union
+from typing import Any, Dict, Optional, Tuple, Union
 
 import torch
 
@@ -96,8 +96,7 @@ class GeneralizedHMC(BaseSampler):
     # routing: decided here and nowhere else
     # ---------------------------------------------------------------------------------
     def _route(self, x: torch.Tensor, model_kwargs=None) -> Tuple[str, Optional[FusedSpec]]:
-        # (model_kwargs: unused -- the signature of the other samplers' _route, which the tests' CPU stand-in replaces)
-        if not x.is_cuda or x.dtype != torch.float32 or x.ndim != 2:
+        if model_kwargs or not x.is_cuda or x.dtype != torch.float32 or x.ndim != 2:
             return "eager", None
         if not self.schedulers["step_size"].is_constant():
             return "eager", None
@@ -125,9 +124,12 @@ class GeneralizedHMC(BaseSampler):
         *,
         velocity: Optional[torch.Tensor] = None,
         return_velocity: bool = False,
+        model_kwargs: Optional[Dict[str, Any]] = None,
         generator: Optional[torch.Generator] = None,
     ):
         """Run ``n_steps`` transitions.
+
+        ``model_kwargs``: conditioning passed to the model at every evaluation; a non-empty dict takes the eager route.
 
         ``velocity``: the start velocities, shaped as ``x`` (as a call with ``return_velocity=True`` returned them: continue
         that run); ``None`` draws them from ``N(0, T I)``.
@@ -151,11 +153,13 @@ class GeneralizedHMC(BaseSampler):
             if tuple(velocity.shape) != tuple(x.shape):
                 raise ValueError(f"velocity must have the state's shape {tuple(x.shape)}, got {tuple(velocity.shape)}")
             velocity = velocity.to(device=self.device, dtype=self.dtype)
-        route, spec = self._route(x, None)
+        model_kwargs = self._prepare_model_kwargs(model_kwargs)
+        route, spec = self._route(x, model_kwargs)
         if route == "fused":
             state, v, traj, diag = self._sample_fused(x, velocity, spec, n_steps, thin, return_trajectory, return_diagnostics, generator)
         else:
-            state, v, traj, diag = self._sample_eager(x, velocity, n_steps, thin, return_trajectory, return_diagnostics, generator)
+            state, v, traj, diag = self._sample_eager(x, velocity, n_steps, thin, return_trajectory, return_diagnostics, generator,
+                                                      model_kwargs)
         out = (traj if return_trajectory else state,)
         if return_diagnostics:
             diag["kinetic_temperature"] = v.square().mean() if v.numel() else torch.full((), float("nan"), dtype=v.dtype, device=v.device)
@@ -203,12 +207,13 @@ class GeneralizedHMC(BaseSampler):
     def _draw_uniform(self, n: int, like: torch.Tensor, generator) -> torch.Tensor:
         return torch.rand(n, dtype=like.dtype, device=like.device, generator=generator)
 
-    def _sample_eager(self, x, v, n_steps, thin, want_traj, want_diag, generator):
+    def _sample_eager(self, x, v, n_steps, thin, want_traj, want_diag, generator, model_kwargs=None):
+        model_kwargs = model_kwargs or {}
         traj, diag = new_outputs(x, x.shape, n_steps // thin, want_traj, want_diag, acceptance=True)
-        energy = lambda x_: self._model_energy(x_, {})  # noqa: E731
+        energy = lambda x_: self._model_energy(x_, model_kwargs)  # noqa: E731
         clamped_energy = lambda x_: energy(x_).clamp_(min=-1e10, max=1e10)  # noqa: E731
         kinetic = lambda v_: (0.5 * torch.sum(v_.flatten(1).square(), dim=-1)).clamp_(min=0.0, max=1e10)  # noqa: E731
-        force = lambda x_: (-self._model_gradient(x_, {})).clamp_(min=-1e6, max=1e6)  # noqa: E731
+        force = lambda x_: (-self._model_gradient(x_, model_kwargs)).clamp_(min=-1e6, max=1e6)  # noqa: E731
         per_chain = lambda m: m.view(-1, *([1] * (x.ndim - 1)))  # noqa: E731
         n, L = x.shape[0], self.n_leapfrog_steps
         if v is None:

@@ -16,8 +16,14 @@ Two execution routes, chosen once per ``sample()`` call (``_route``):
 ``fused``  CUDA fp32 state, no autocast, one of the analytic energies (not the MLP), ``dim <= 256`` and a constant step size:
            the whole call -- start velocities, steps, Philox draws, thinned trajectory -- is ONE launch of
            ``ebm_kinetic_chain_f32`` (include/ebm_hip.h states the recurrence exactly; docs/design/kinetic.md the kernel).
-``eager``  everything else (CPU, any other ``BaseModel``, a scheduler on ``step_size``, wider rows): the same recurrence in
-           torch ops around ``model.gradient``, drawing ``randn(n, dim)`` for the start velocities and once per step.
+``fused_mlp``  opt-in (``sampler.fused_mlp = True``): CUDA fp32 state, no autocast, a constant step size, an ``MLPEnergy`` of
+           hidden width 64 / 128 and ``dim == in_dim <= 128``: the whole call is ONE launch of ``ebm_kinetic_mlp_chain_f32``
+           (docs/design/kinetic_mlp.md), the evaluation on the matrix cores inside the step loop.  Its gradients are the kernel's
+           (fp32-accurate, not autograd's rounding) and its draws the Philox field's, so the default stays ``eager`` for the MLP
+           and a call made without the opt-in is bit for bit what it was.
+``eager``  everything else (CPU, any other ``BaseModel``, a scheduler on ``step_size``, wider rows, ``model_kwargs``): the same
+           recurrence in torch ops around ``model.gradient``, drawing ``randn(n, dim)`` for the start velocities and once per
+           step.
 
 A fused-eligible call never falls back to eager: a missing library or a failing launch raises.
 """
@@ -25,7 +31,7 @@ A fused-eligible call never falls back to eager: a missing library or a failing 
 from __future__ import annotations
 
 import math
-from typing import Optional, Tuple, Union
+from typing import Any, Dict, Optional, Tuple, Union
 
 import torch
 
@@ -56,6 +62,11 @@ class UnderdampedLangevin(BaseSampler):
         dtype, device: where the chains live.
     """
 
+    #: opt-in: an ``MLPEnergy`` (hidden 64 / 128, ``dim == in_dim <= 128``, CUDA fp32, no autocast, a constant step size) runs as
+    #: ONE launch of ``ebm_kinetic_mlp_chain_f32`` instead of the eager route.  Off by default: the fused evaluation is
+    #: three-way-split bf16 arithmetic at fp32 accuracy, not autograd's rounding, and the draws are the Philox field's, not torch's.
+    fused_mlp = False
+
     def __init__(
         self,
         model: BaseModel,
@@ -78,15 +89,19 @@ class UnderdampedLangevin(BaseSampler):
     # routing: decided here and nowhere else
     # ---------------------------------------------------------------------------------
     def _route(self, x: torch.Tensor, model_kwargs=None) -> Tuple[str, Optional[FusedSpec]]:
-        # (model_kwargs: unused -- the signature of the other samplers' _route, which the tests' CPU stand-in replaces)
-        if not x.is_cuda or x.dtype != torch.float32 or x.ndim != 2:
+        if model_kwargs or not x.is_cuda or x.dtype != torch.float32 or x.ndim != 2:
             return "eager", None
         if not self.schedulers["step_size"].is_constant():
             return "eager", None
         if self.use_mixed_precision and self.autocast_available:
             return "eager", None
         spec = fused_spec_for(self.model, x, None)
-        if spec is None or spec.kind == _lib.ENERGY_MLP or x.shape[1] > FUSED_MAX_DIM:
+        if spec is None or x.shape[1] > FUSED_MAX_DIM:
+            return "eager", None
+        if spec.kind == _lib.ENERGY_MLP:
+            dim = x.shape[1]
+            if self.fused_mlp and spec.n_comp in (64, 128) and dim == getattr(self.model, "in_dim", None) and dim <= 128:
+                return "fused_mlp", spec
             return "eager", None
         return "fused", spec
 
@@ -107,9 +122,12 @@ class UnderdampedLangevin(BaseSampler):
         *,
         velocity: Optional[torch.Tensor] = None,
         return_velocity: bool = False,
+        model_kwargs: Optional[Dict[str, Any]] = None,
         generator: Optional[torch.Generator] = None,
     ):
         """Run ``n_steps`` BAOAB steps.
+
+        ``model_kwargs``: conditioning passed to the model at every evaluation; a non-empty dict takes the eager route.
 
         ``velocity``: the start velocities, shaped as ``x`` (as a call with ``return_velocity=True`` returned them: continue
         that run); ``None`` draws them from ``N(0, T I)``.
@@ -133,11 +151,16 @@ class UnderdampedLangevin(BaseSampler):
             if tuple(velocity.shape) != tuple(x.shape):
                 raise ValueError(f"velocity must have the state's shape {tuple(x.shape)}, got {tuple(velocity.shape)}")
             velocity = velocity.to(device=self.device, dtype=self.dtype)
-        route, spec = self._route(x, None)
+        model_kwargs = self._prepare_model_kwargs(model_kwargs)
+        route, spec = self._route(x, model_kwargs)
         if route == "fused":
             state, v, traj, diag = self._sample_fused(x, velocity, spec, n_steps, thin, return_trajectory, return_diagnostics, generator)
+        elif route == "fused_mlp":
+            state, v, traj, diag = self._sample_fused(x, velocity, spec, n_steps, thin, return_trajectory, return_diagnostics, generator,
+                                                      entry="ebm_kinetic_mlp_chain_f32")
         else:
-            state, v, traj, diag = self._sample_eager(x, velocity, n_steps, thin, return_trajectory, return_diagnostics, generator)
+            state, v, traj, diag = self._sample_eager(x, velocity, n_steps, thin, return_trajectory, return_diagnostics, generator,
+                                                      model_kwargs)
         out = (traj if return_trajectory else state,)
         if return_diagnostics:
             diag["kinetic_temperature"] = v.square().mean() if v.numel() else torch.full((), float("nan"), dtype=v.dtype, device=v.device)
@@ -179,15 +202,16 @@ class UnderdampedLangevin(BaseSampler):
     # ---------------------------------------------------------------------------------
     # route: torch ops
     # ---------------------------------------------------------------------------------
-    def _sample_eager(self, x, v, n_steps, thin, want_traj, want_diag, generator):
+    def _sample_eager(self, x, v, n_steps, thin, want_traj, want_diag, generator, model_kwargs=None):
+        model_kwargs = model_kwargs or {}
         traj, diag = new_outputs(x, x.shape, n_steps // thin, want_traj, want_diag)
-        energy = lambda x_: self._model_energy(x_, {})  # noqa: E731
+        energy = lambda x_: self._model_energy(x_, model_kwargs)  # noqa: E731
         if v is None:
             sqrt_temp = baoab_constants(1.0, self.friction, self.temperature, x.dtype)[3]
             v = sqrt_temp * torch.randn(x.shape, dtype=x.dtype, device=x.device, generator=generator)
         keep = 0
         with self.autocast_context():
-            g = self._model_gradient(x, {})
+            g = self._model_gradient(x, model_kwargs)
             for s in range(n_steps):
                 hh, c1, c2, _ = baoab_constants(self.get_scheduled_value("step_size"), self.friction, self.temperature, x.dtype)
                 xi = torch.randn(x.shape, dtype=x.dtype, device=x.device, generator=generator)
@@ -196,7 +220,7 @@ class UnderdampedLangevin(BaseSampler):
                 x = x + hh * v
                 v = c1 * v + c2 * xi
                 x = x + hh * v
-                g = self._model_gradient(x, {})
+                g = self._model_gradient(x, model_kwargs)
                 v = v - hh * g
                 self.step_schedulers()
                 if (s + 1) % thin == 0:
@@ -207,9 +231,9 @@ class UnderdampedLangevin(BaseSampler):
         return x, v, traj, diag
 
     # ---------------------------------------------------------------------------------
-    # route: one launch of ebm_kinetic_chain_f32
+    # routes: one launch of ebm_kinetic_chain_f32, or (fused_mlp) of ebm_kinetic_mlp_chain_f32 -- the same parameter list
     # ---------------------------------------------------------------------------------
-    def _sample_fused(self, x, v, spec: FusedSpec, n_steps, thin, want_traj, want_diag, generator):
+    def _sample_fused(self, x, v, spec: FusedSpec, n_steps, thin, want_traj, want_diag, generator, entry: str = "ebm_kinetic_chain_f32"):
         n, dim = x.shape
         n_kept = n_steps // thin
         state = _lib.dense_f32(x).clone()  # the kernel updates in place; never the caller's tensors
@@ -222,7 +246,7 @@ class UnderdampedLangevin(BaseSampler):
         spec_c = spec.to_c()
         if n > 0 and n_steps > 0:
             _lib.call(
-                "ebm_kinetic_chain_f32",
+                entry,
                 spec_c, _lib.ptr(state), _lib.ptr(vel), n, dim, n_steps, self.get_scheduled_value("step_size"), self.friction,
                 self.temperature, int(draw_v0), thin, _lib.ptr(traj) if need_kept else None, None, seed, step0, stream,
             )
@@ -236,5 +260,9 @@ class UnderdampedLangevin(BaseSampler):
         if want_diag:
             diag = new_outputs(state, state.shape, n_kept, False, True)[1]
             if n > 0 and n_kept > 0:
-                kept_statistics(spec_c, traj, diag, stream)
+                if spec.kind == _lib.ENERGY_MLP:  # the kept positions' statistics in torch ops, their energy the model's
+                    for keep in range(n_kept):
+                        record_kept(traj[:, keep], keep, None, diag, lambda x_: self._model_energy(x_, {}))
+                else:
+                    kept_statistics(spec_c, traj, diag, stream)
         return state, vel, (traj if want_traj else None), diag
