@@ -643,6 +643,58 @@ EBM_API int ebm_ghmc_chain_f32(const ebm_energy_t* energy, float* x, float* v, i
                                uint64_t seed, uint64_t offset, void* stream);
 
 /*
+ * Generalized HMC on the MLP energy: the sampler of ebm_ghmc_chain_f32 above -- the same parameter list, the same constants
+ * formed in double and rounded once (c1, c2, sqrt_temp, beta, eps), the same Philox coordinates -- with the matrix-core
+ * evaluation of ebm_hmc_chain_f32 / ebm_ais_mlp_chain_f32 inside the trajectory, in ONE launch (an addition to ABI 9: nothing
+ * else moved; ebm_ghmc_chain_f32 still refuses the MLP).  One wave walks 32 chains.
+ *
+ * State.  The held x and v live in the caller's x / v buffers between transitions (a lane reads back only what it stored
+ * itself); no energy and no force is carried from one transition to the next.
+ *
+ * Transition t = 0 .. n_mh - 1, the contract above restated for this evaluation (the transition of ebm_ais_mlp_chain_f32 at
+ * beta = 1 around the refresh and the flip):
+ *     v  = c1 * v + c2 * z_t                       (O)  two products and a sum, each rounded on its own; v is stored back
+ *     E, g = the evaluation at the held x;  f = clamp(-g, +-1e6)
+ *     H0 = clamp(E, +-1e10) + clamp(0.5 sum v^2, 0, 1e10)
+ *     n_leapfrog times:  v = fma(eps / 2, f, v);  x' = fma(eps, v, x');  E', g' = the evaluation at x';
+ *                        f = clamp(-g', +-1e6);  v = fma(eps / 2, f, v)       -- the two half kicks are never merged
+ *         (where E' or g' is not finite in some chain of the wave: the NaN-propagating clamp, v and x' scrubbed with
+ *          nan_to_num(nan = 0), and E', f re-evaluated on the scrubbed x' -- the literal safe-mode step; a NaN in v alone is
+ *          scrubbed in place)
+ *     H1 = clamp(E', +-1e10) + clamp(0.5 sum v^2, 0, 1e10)
+ *     d  = clamp(beta * (H0 - H1), +-50);  a = min(1, exp d);  accepted iff u < a (a NaN rejects)
+ *     accepted:  x = x', v = v' are stored
+ *     rejected:  x stays;  v = -(the stored v after O)                                           the flip
+ * A transition makes n_leapfrog + 1 evaluations.
+ *
+ * Draws.  A call owns the Philox steps offset .. offset + 2 n_mh.  z_t is the normal field at step offset + 1 + 2 t, element
+ * chain * dim + col; u the uniform field at step offset + 2 + 2 t, element chain.  draw_v0 != 0: v is output only and the walk
+ * starts from sqrt_temp * z, z the normal field at step offset (also when draws are injected); draw_v0 == 0: v is read.
+ * noise: NULL, or float[n_mh][n_chains][dim] in place of z_t; u: NULL, or float[n_mh][n_chains] in place of the uniforms; either
+ * may be given without the other.
+ *
+ * Outputs.  x and v hold the final state.  traj: NULL, or float[n_chains][n_mh / thin][dim], the held position after
+ * transition t whenever (t + 1) % thin == 0.  accept_mask: NULL, or uint8[n_mh][n_chains] (1 = accepted).  Columns past dim and
+ * rows past n_chains never reach memory; 64-bit row indices.
+ *
+ * Two calls equal one: (n1, offset) then (n2, offset + 2 n1) with draw_v0 = 0 produces the bits of one call of n1 + n2 -- nothing
+ * but x and v passes from one transition to the next.
+ *
+ * The evaluation is three-way split bf16 (or exact-f32 MFMA) arithmetic with fp32 accumulation: fp32 accuracy, not autograd's
+ * rounding.
+ *
+ * Refusals, all in front of any device access and of the early return for n_chains == 0: a NULL energy, x or v, n_mh < 1,
+ * n_leapfrog < 1, thin < 1, n_chains < 0, eps, gamma or temperature not positive, or NaN, a non-finite eps or temperature
+ * (EBM_EINVAL; gamma = +inf is allowed); a kind other than EBM_ENERGY_MLP (EBM_EKIND); a hidden width (energy->n_comp) other than
+ * 64 / 128 or dim outside 1 .. 128 (EBM_EDIM, the message names both).  x, v, traj and noise must be 16-byte aligned.  No
+ * H = 256, no pre-split W1 image (energy->aux is ignored), no tables, no mass matrix, no diagnostics records.
+ */
+EBM_API int ebm_ghmc_mlp_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t n_mh,
+                                   int32_t n_leapfrog, double eps, double gamma, double temperature, int32_t draw_v0,
+                                   int32_t thin, float* traj, uint8_t* accept_mask, const float* noise, const float* u,
+                                   uint64_t seed, uint64_t offset, void* stream);
+
+/*
  * Per-chain running moments of the two velocity-carrying samplers: k_steps transitions of the BAOAB walker of
  * ebm_kinetic_chain_f32 (sampler = 0) or of the generalized-HMC walker of ebm_ghmc_chain_f32 (sampler = 1) per chain that
  * keeps, beside position and velocity, the Welford pairs of ebm_chain_moments_f32 in registers, in ONE launch (an addition to

@@ -48,6 +48,7 @@ EXPORTS = (
     "ebm_kinetic_chain_f32",
     "ebm_kinetic_mlp_chain_f32",
     "ebm_ghmc_chain_f32",
+    "ebm_ghmc_mlp_chain_f32",
     "ebm_kinetic_moments_f32",
     "ebm_leapfrog_kick_drift_f32",
     "ebm_leapfrog_kick_f32",
@@ -161,6 +162,10 @@ _PROTOTYPES = {
     # (the same parameter list, on the MLP energy)
     "ebm_kinetic_mlp_chain_f32": (C.c_int, [_ENERGY_P, _p, _p, _i64, _i32, _i32, _d, _d, _d, _i32, _i32, _p, _p, _u64, _u64, _p]),
     "ebm_ghmc_chain_f32": (
+        C.c_int,
+        [_ENERGY_P, _p, _p, _i64, _i32, _i32, _i32, _d, _d, _d, _i32, _i32, _p, _p, _p, _p, _u64, _u64, _p],
+    ),
+    "ebm_ghmc_mlp_chain_f32": (
         C.c_int,
         [_ENERGY_P, _p, _p, _i64, _i32, _i32, _i32, _d, _d, _d, _i32, _i32, _p, _p, _p, _p, _u64, _u64, _p],
     ),

@@ -580,6 +580,21 @@ int ebm_kinetic_mlp_chain_f32(const ebm_energy_t* energy, float* x, float* v, in
                                   (hipStream_t)stream);
 }
 
+// The request of both generalized-HMC entries: the constants of the refresh over one trajectory's time eps L, formed in double,
+// each rounded once (gamma = +inf: c1 = 0 and c2 = sqrt_temp exactly)
+static GhmcChainReq ghmc_request(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t n_mh,
+                                 int32_t n_leapfrog, double eps, double gamma, double temperature, int32_t draw_v0, int32_t thin,
+                                 float* traj, uint8_t* accept_mask, const float* noise, const float* u, uint64_t seed,
+                                 uint64_t offset) {
+  const double span = gamma * eps * (double)n_leapfrog;
+  const float sqrt_temp = (float)sqrt(temperature);
+  const float c1 = std::isinf(gamma) ? 0.0f : (float)exp(-span);
+  const float c2 = std::isinf(gamma) ? sqrt_temp : (float)sqrt(temperature * (-expm1(-2.0 * span)));
+  const float beta = (float)(1.0 / temperature);
+  return GhmcChainReq{*energy, x, v, n_chains, dim, n_mh, n_leapfrog, (float)eps, c1, c2, sqrt_temp, beta, draw_v0 != 0, thin, traj,
+                      accept_mask, noise, u, seed, offset};
+}
+
 int ebm_ghmc_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t n_mh,
                        int32_t n_leapfrog, double eps, double gamma, double temperature, int32_t draw_v0, int32_t thin,
                        float* traj, uint8_t* accept_mask, const float* noise, const float* u, uint64_t seed, uint64_t offset,
@@ -600,15 +615,36 @@ int ebm_ghmc_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n
   if (n_chains == 0) return 0;
   if (!aligned16(v) || (traj && !aligned16(traj)) || (noise && !aligned16(noise)))
     return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
-  // the constants of the refresh over one trajectory's time eps L: formed in double, each rounded once
-  const double span = gamma * eps * (double)n_leapfrog;
-  const float sqrt_temp = (float)sqrt(temperature);
-  const float c1 = std::isinf(gamma) ? 0.0f : (float)exp(-span);
-  const float c2 = std::isinf(gamma) ? sqrt_temp : (float)sqrt(temperature * (-expm1(-2.0 * span)));
-  const float beta = (float)(1.0 / temperature);
-  const GhmcChainReq q{*energy, x, v, n_chains, dim, n_mh, n_leapfrog, (float)eps, c1, c2, sqrt_temp, beta, draw_v0 != 0, thin, traj,
-                       accept_mask, noise, u, seed, offset};
-  return ghmc_chain_launch(q, (hipStream_t)stream);
+  return ghmc_chain_launch(ghmc_request(energy, x, v, n_chains, dim, n_mh, n_leapfrog, eps, gamma, temperature, draw_v0, thin, traj,
+                                        accept_mask, noise, u, seed, offset),
+                           (hipStream_t)stream);
+}
+
+int ebm_ghmc_mlp_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t n_mh,
+                           int32_t n_leapfrog, double eps, double gamma, double temperature, int32_t draw_v0, int32_t thin,
+                           float* traj, uint8_t* accept_mask, const float* noise, const float* u, uint64_t seed, uint64_t offset,
+                           void* stream) {
+  const char* who = "ebm_ghmc_mlp_chain_f32";
+  if (int r = check_energy(energy, dim, who)) return r;
+  if (energy->kind != EBM_ENERGY_MLP)
+    return fail(EBM_EKIND, "%s: this entry walks the MLP energy only (ebm_ghmc_chain_f32 takes the analytic kinds)", who);
+  // (the dim range is ghmc_mlp_check_shape's to refuse)
+  if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
+  if (!v) return fail(EBM_EINVAL, "%s: velocity pointer is NULL", who);
+  if (n_chains < 0) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d]", who, (long long)n_chains, dim);
+  if (n_mh < 1 || n_leapfrog < 1 || thin < 1)
+    return fail(EBM_EINVAL, "%s: n_mh=%d n_leapfrog=%d thin=%d (all must be >= 1)", who, n_mh, n_leapfrog, thin);
+  // (gamma = +inf is allowed: a full refresh, the HMC transition)
+  if (!(eps > 0.0) || !(gamma > 0.0) || !(temperature > 0.0) || !std::isfinite(eps) || !std::isfinite(temperature))
+    return fail(EBM_EINVAL, "%s: eps=%g gamma=%g temperature=%g (all must be positive; eps and temperature finite)", who, eps, gamma,
+                temperature);
+  if (int r = ghmc_mlp_check_shape(energy->n_comp, dim)) return r;
+  if (n_chains == 0) return 0;
+  if (!aligned16(x) || !aligned16(v) || (traj && !aligned16(traj)) || (noise && !aligned16(noise)))
+    return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  return ghmc_mlp_chain_launch(ghmc_request(energy, x, v, n_chains, dim, n_mh, n_leapfrog, eps, gamma, temperature, draw_v0, thin,
+                                            traj, accept_mask, noise, u, seed, offset),
+                               (hipStream_t)stream);
 }
 
 int ebm_kinetic_moments_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t sampler,

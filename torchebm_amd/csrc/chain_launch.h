@@ -341,6 +341,9 @@ int kinetic_mlp_check_shape(int32_t hidden, int32_t dim);  // 0, or the refusal 
 // ---------------------------------------------------------------------------------
 int ghmc_chain_launch(const GhmcChainReq&, hipStream_t);
 int ghmc_check_geometry(int32_t dim);  // 0, or the refusal (dim > 256)
+// ... on the MLP energy (mlp_wide_ghmc.hip: the same request; 32 chains per wave around the matrix-core evaluation, n_leapfrog + 1 of them per transition)
+int ghmc_mlp_chain_launch(const GhmcChainReq&, hipStream_t);
+int ghmc_mlp_check_shape(int32_t hidden, int32_t dim);  // 0, or the refusal (hidden width not 64 / 128, dim outside 1 .. 128)
 
 // ---------------------------------------------------------------------------------
 // Running moments of the two (kinetic_moments.hip: the BAOAB or the GHMC walker with Welford pairs beside position and velocity)

@@ -14,12 +14,16 @@ chain samples ``exp(-E / T)`` exactly for every step size, as ``HamiltonianMonte
 sampler's transition), and with weak friction it keeps its direction across transitions, as ``UnderdampedLangevin`` does --
 which is unadjusted and leaves a step-size bias.
 
-Two execution routes, chosen once per ``sample()`` call (``_route``):
+Three execution routes, chosen once per ``sample()`` call (``_route``):
 
 ``fused``  CUDA fp32 2-D state, no autocast, one of the analytic energies (not the MLP), ``dim <= 256`` and a constant step size:
            the whole call -- start velocities, refreshes, trajectories, decisions, Philox draws, thinned trajectory, accept mask
            -- is ONE launch of ``ebm_ghmc_chain_f32`` (include/ebm_hip.h states the recurrence exactly; docs/design/ghmc.md
            the kernel).
+``fused_mlp``  the same state and step size on an ``MLPEnergy`` of hidden width 64 / 128 and ``in_dim <= 128``, and ONLY with the
+           opt-in ``sampler.fused_mlp = True``: ONE launch of ``ebm_ghmc_mlp_chain_f32`` (docs/design/ghmc_mlp.md) -- the same
+           recurrence, the same Philox coordinates, the matrix-core evaluation inside the trajectory; fp32 accuracy, not
+           autograd's rounding.  Off by default: a default sampler on an MLP keeps its eager bits.
 ``eager``  everything else (CPU, any other ``BaseModel``, a scheduler on ``step_size``, wider rows): the same recurrence in
            torch ops around ``model`` / ``model.gradient`` with the clamps of ``HamiltonianMonteCarlo``'s eager transition,
            drawing ``randn(n, dim)`` for the start velocities (only when none are passed) and ``randn(n, dim)``, ``rand(n)``
@@ -42,6 +46,7 @@ from ..core.schedules import BaseScheduler
 from ._chain_host import kept_statistics, new_outputs, record_kept
 
 FUSED_MAX_DIM = 256  # one vector per lane (csrc/ghmc.hip)
+FUSED_MLP_MAX_DIM = 128  # four state tiles of 32 columns (csrc/mlp_wide_ghmc.hip)
 
 
 def ghmc_constants(eps: float, n_leapfrog: int, friction: float, temperature: float,
@@ -68,7 +73,12 @@ class GeneralizedHMC(BaseSampler):
         friction: friction ``gamma > 0``; the velocity keeps ``exp(-gamma eps L)`` of itself per transition, ``inf`` is HMC.
         temperature: temperature ``T > 0``; the chains sample ``exp(-E / T)``.
         dtype, device: where the chains live.
+
+    ``fused_mlp`` (class attribute, ``False``): set it on a sampler to send an eligible ``MLPEnergy`` call to the one-launch
+    route ``fused_mlp`` (module docstring).
     """
+
+    fused_mlp = False
 
     def __init__(
         self,
@@ -103,7 +113,12 @@ class GeneralizedHMC(BaseSampler):
         if self.use_mixed_precision and self.autocast_available:
             return "eager", None
         spec = fused_spec_for(self.model, x, None)
-        if spec is None or spec.kind == _lib.ENERGY_MLP or x.shape[1] > FUSED_MAX_DIM:
+        if spec is None or x.shape[1] > FUSED_MAX_DIM:
+            return "eager", None
+        if spec.kind == _lib.ENERGY_MLP:
+            dim = x.shape[1]
+            if self.fused_mlp and spec.n_comp in (64, 128) and dim == getattr(self.model, "in_dim", None) and dim <= FUSED_MLP_MAX_DIM:
+                return "fused_mlp", spec
             return "eager", None
         return "fused", spec
 
@@ -157,6 +172,9 @@ class GeneralizedHMC(BaseSampler):
         route, spec = self._route(x, model_kwargs)
         if route == "fused":
             state, v, traj, diag = self._sample_fused(x, velocity, spec, n_steps, thin, return_trajectory, return_diagnostics, generator)
+        elif route == "fused_mlp":
+            state, v, traj, diag = self._sample_fused(x, velocity, spec, n_steps, thin, return_trajectory, return_diagnostics, generator,
+                                                      entry="ebm_ghmc_mlp_chain_f32")
         else:
             state, v, traj, diag = self._sample_eager(x, velocity, n_steps, thin, return_trajectory, return_diagnostics, generator,
                                                       model_kwargs)
@@ -251,9 +269,9 @@ class GeneralizedHMC(BaseSampler):
         return x, v, traj, diag
 
     # ---------------------------------------------------------------------------------
-    # route: one launch of ebm_ghmc_chain_f32
+    # routes: one launch of ebm_ghmc_chain_f32, or (fused_mlp) of ebm_ghmc_mlp_chain_f32 -- the same parameter list
     # ---------------------------------------------------------------------------------
-    def _sample_fused(self, x, v, spec: FusedSpec, n_steps, thin, want_traj, want_diag, generator):
+    def _sample_fused(self, x, v, spec: FusedSpec, n_steps, thin, want_traj, want_diag, generator, entry: str = "ebm_ghmc_chain_f32"):
         n, dim = x.shape
         n_kept = n_steps // thin
         state = _lib.dense_f32(x).clone()  # the kernel updates in place; never the caller's tensors
@@ -267,7 +285,7 @@ class GeneralizedHMC(BaseSampler):
         spec_c = spec.to_c()
         if n > 0 and n_steps > 0:
             _lib.call(
-                "ebm_ghmc_chain_f32",
+                entry,
                 spec_c, _lib.ptr(state), _lib.ptr(vel), n, dim, n_steps, self.n_leapfrog_steps, self.get_scheduled_value("step_size"),
                 self.friction, self.temperature, int(draw_v0), thin, _lib.ptr(traj) if need_kept else None, _lib.ptr(mask), None, None,
                 seed, step0, stream,
@@ -282,6 +300,10 @@ class GeneralizedHMC(BaseSampler):
         if want_diag:
             diag = new_outputs(state, state.shape, n_kept, False, True, acceptance=True)[1]
             if n > 0 and n_kept > 0:
-                kept_statistics(spec_c, traj, diag, stream)
+                if spec.kind == _lib.ENERGY_MLP:  # the kept positions' statistics in torch ops, their energy the model's
+                    for keep in range(n_kept):
+                        record_kept(traj[:, keep], keep, None, diag, lambda x_: self._model_energy(x_, {}))
+                else:
+                    kept_statistics(spec_c, traj, diag, stream)
                 diag["acceptance_rate"].copy_(mask[thin - 1 :: thin][:n_kept].float().mean(dim=1))
         return state, vel, (traj if want_traj else None), diag
