@@ -28,6 +28,7 @@ CASES = [
     (30, 128, 257, 1, 1, 3),
     (32, 64, 129, 6, 3, 1),
     (33, 128, 37, 4, 2, 3),
+    (40, 64, 37, 4, 2, 1),
     (64, 128, 129, 4, 2, 1),
     (65, 64, 37, 1, 1, 3),
     (96, 128, 37, 4, 2, 1),

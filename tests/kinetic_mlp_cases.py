@@ -24,6 +24,7 @@ CASES = [
     (30, 128, 257, 1, 1),
     (32, 64, 129, 11, 3),
     (33, 128, 37, 4, 2),
+    (40, 64, 37, 4, 2),
     (64, 128, 129, 4, 2),
     (65, 64, 37, 1, 1),
     (96, 128, 37, 4, 2),

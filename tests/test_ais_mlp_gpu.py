@@ -26,6 +26,7 @@ CASES = [
     (32, 128, 70, 4),
     (33, 64, 37, 4),     # DT = 2 with one live column in the second tile
     (64, 128, 37, 4),
+    (70, 64, 37, 3),     # H = 64 at DT = 3
     (100, 128, 37, 3),   # mode 0
     (128, 64, 37, 3),
     (128, 128, 33, 2),   # mode 0

@@ -30,7 +30,7 @@ int ais_mlp_chain_launch(const AisChainReq& q, hipStream_t st) {
   a.accept_mask = q.accept_mask; a.accept_counts = q.accept_counts;
   a.x0 = q.x0; a.p_noise = q.p_noise; a.u_accept = q.u_accept; a.key = q.key(); a.step0 = q.offset;
   a.params = q.e.dev0;
-  if (q.e.n_comp == 64) return widemlp::launch_ais_hidden<2>(a, st, who);
+  if (q.e.n_comp == 64) return widemlp::launch_walk_by_dim<widemlp::AisWalk, 2>(a, st, who);
   return launch_ais_mlp_wide_h128(a, st, who);
 }
 

@@ -1,10 +1,10 @@
 // Kernel body of annealed importance sampling on the wide MLP energy (ebm_ais_mlp_chain_f32, include/ebm_hip.h;
-// docs/design/ais_mlp.md): the transition state machine of mlp_wide_hmc_body.h -- mode 0: E and dE/dx at the held state,
-// mode 1: after a kick + drift, mode 2: re-evaluation on a scrubbed position, decided per wave -- with the PATH energy
+// docs/design/ais_mlp.md): the ladder, the momentum draw, the accept and the chain's importance weight (a Kahan pair) put around
+// the shared leapfrog state machine (mlp_wide_leapfrog.inc) walking the PATH energy
 //   U_b(x) = (1 - b) E_0(x) + b E(x),   E_0(x) = 0.5 inv_var0 sum x^2
-// put around the one evaluation (mlp_wide_setup.inc, mlp_wide_eval.inc), and the chain's importance weight carried as a Kahan
-// pair.  One wave is 32 chains; state, momentum and force live in the 32x32 C/D layout of the evaluation.  Two translation
-// units instantiate it (compiled in parallel): mlp_wide_ais.hip (H = 64) and mlp_wide_ais_h128.hip (H = 128).
+// and through it around the one evaluation (mlp_wide_setup.inc, mlp_wide_eval.inc); rows, noise and the launch are
+// mlp_wide_rows.h's.  One wave is 32 chains; state, momentum and force live in the 32x32 C/D layout of the evaluation.  Two
+// translation units instantiate it (compiled in parallel): mlp_wide_ais.hip (H = 64) and mlp_wide_ais_h128.hip (H = 128).
 //
 // A transition is n_leapfrog + 1 evaluations, as the HMC sibling's: the mode-0 evaluation at the top of step t is where the weight
 // update takes E(x) from.  (Carrying E and the raw gradient of an accepted proposal to the next step would save it, at 16 DT + 1
@@ -12,7 +12,7 @@
 // The mix is (1 - b) * a + b * c in separately rounded operations, never divided by b: at b = 1 it is 0 * a + 1 * c = c, and the
 // transition is mlp_wide_hmc_kernel's (general variant, identity mass) bit for bit.
 #pragma once
-#include "mlp_wide_body.h"
+#include "mlp_wide_rows.h"
 
 namespace ebm {
 namespace widemlp {
@@ -41,41 +41,15 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_ais_chain(WideAisArgs a) {
   static_assert(MODE == 0 || MODE == 2, "weights in LDS: fp32 (0) or split bf16 images (2)");
   constexpr bool EVAL_SCALED = false;
 #include "mlp_wide_setup.inc"
-  // The images' LDS addresses, formed once: an opaque scalar each.  (Left visible, the conversion of the LDS pointer is
-  // re-derived at its uses inside the evaluation when registers run out -- H = 128 at two state tiles -- in a form the
-  // backend rejects.)
-  auto walk1_once = walk1;
-  auto walk2_once = walk2;
-  asm volatile("" : "+s"(walk1_once.base), "+s"(walk2_once.base));
+  EBM_WIDE_WALKS_ONCE_OPAQUE();  // (mlp_wide_rows.h)
+  EBM_WIDE_LANES();
+  const int& hq = h;  // the lane's K-half as the shared text names it (not opaque in this kernel)
 
-  // rows of a [.., dim] matrix into the C/D layout, zero beyond dim and for the lanes past the last chain
-  auto load_rows = [&](float (&dst)[DT][16], const float* src, int64_t row) {
-#pragma unroll
-    for (int td = 0; td < DT; ++td)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int c0 = 32 * td + 8 * q + 4 * h;
-        if (quads && active && c0 + 3 < dim) {
-          const float4 v = *reinterpret_cast<const float4*>(src + row * dim + c0);
-          dst[td][4 * q] = v.x; dst[td][4 * q + 1] = v.y; dst[td][4 * q + 2] = v.z; dst[td][4 * q + 3] = v.w;
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) dst[td][4 * q + i] = (active && c0 + i < dim) ? src[row * dim + c0 + i] : 0.0f;
-        }
-      }
-  };
-  // the held state lives in a.x between transitions (as in mlp_wide_hmc_body.h); a lane reads back only what it stored itself
-  auto store_state = [&](const float (&src)[DT][16], int64_t row) {
-#pragma unroll
-    for (int td = 0; td < DT; ++td)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int c = 32 * td + row_of(r, h);
-        if (c < dim) a.x[row * dim + c] = src[td][r];
-      }
-  };
-  // the normal field at `step`, element chain * dim + col, in the C/D layout (zero beyond dim): per quad where a register quad
-  // is one Philox counter, per element otherwise
+  // Three helpers this kernel keeps in its own words -- the field is normal_quad's, the store store_rows', the sum sum_squares' of
+  // mlp_wide_rows.h: through those, with the shared loop, the H = 128, dim 33 .. 64 kernel takes 8 bytes more scratch (200 -> 208,
+  // two more spills); spelled here no kernel of the family spills more than it did (docs/design/mlp_wide.md).
+  // the normal field at `step`, element chain * dim + col, in the C/D layout (zero beyond dim): per quad where a register quad is
+  // one Philox counter, per element otherwise
   auto normal_rows = [&](float (&dst)[DT][16], int64_t row, uint64_t step) {
 #pragma unroll
     for (int td = 0; td < DT; ++td)
@@ -107,15 +81,15 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_ais_chain(WideAisArgs a) {
         for (int i = 0; i < 4; ++i) dst[td][4 * q + i] = (c0 + i < dim) ? z[i] : 0.0f;
       }
   };
-  // 0.5 p^T p over the whole chain (both K-halves), clamped to [0, 1e10]
-  auto kinetic = [&](const float (&q)[DT][16]) -> float {
-    float acc = 0.0f;
+  // the held state lives in a.x between transitions (as in mlp_wide_hmc_body.h); a lane reads back only what it stored itself
+  auto store_state = [&](const float (&src)[DT][16], int64_t row) {
 #pragma unroll
     for (int td = 0; td < DT; ++td)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc += q[td][r] * q[td][r];
-    acc += __shfl_xor(acc, 32);
-    return clamp_nanprop(0.5f * acc, 0.0f, 1e10f);
+      for (int r = 0; r < 16; ++r) {
+        const int c = 32 * td + row_of(r, h);
+        if (c < dim) a.x[row * dim + c] = src[td][r];
+      }
   };
   // E_0 = 0.5 inv_var0 sum x^2 (the padding registers are zero)
   const float half_inv_var0 = 0.5f * a.inv_var0;
@@ -133,7 +107,7 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_ais_chain(WideAisArgs a) {
   {
     float xs[DT][16];
     if (a.x0) {
-      load_rows(xs, a.x0, sample);
+      load_rows(lanes, xs, a.x0, sample);
     } else {
       normal_rows(xs, sample, a.step0);
 #pragma unroll
@@ -158,110 +132,26 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_ais_chain(WideAisArgs a) {
 
     // ---- momentum draw p ~ N(0, I)
     float p[DT][16];
-    if (a.p_noise) load_rows(p, a.p_noise + (int64_t)(t - 1) * a.n_chains * dim, smp);
+    if (a.p_noise) load_rows(lanes, p, a.p_noise + (int64_t)(t - 1) * a.n_chains * dim, smp);
     else normal_rows(p, smp, a.step0 + 2ull * (uint64_t)t - 1ull);
 
-    float xr[DT][16], f[DT][16];
-    load_rows(xr, a.x, smp);
-#pragma unroll
-    for (int td = 0; td < DT; ++td)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) f[td][r] = 0.0f;
-    float h0 = 0.0f, e_last = 0.0f;
-    int done = 0, mode = 0;  // wave-uniform
-    while (done <= a.n_leapfrog) {
-      if (mode == 1) {  // first half kick + drift
-#pragma unroll
-        for (int td = 0; td < DT; ++td)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float ph = __builtin_fmaf(half_eps, f[td][r], p[td][r]);
-            p[td][r] = ph;
-            const float xn = __builtin_fmaf(eps, ph, xr[td][r]);
-            xr[td][r] = (32 * td + row_of(r, h) < dim) ? xn : 0.0f;
-          }
-      }
-      constexpr bool eval_energy_only = false, eval_block_cuts = false, eval_store_acts = false, eval_need_energy = true, eval_pin = false;
-      [[maybe_unused]] float* const act_base = nullptr;
-      [[maybe_unused]] constexpr uint32_t act_lane = 0;
-      [[maybe_unused]] constexpr float act_seed = 1.0f;
-      [[maybe_unused]] const auto eval_aux = [](auto) __attribute__((always_inline)) {};
-      [[maybe_unused]] constexpr bool slab_more = true;
-      const auto& walk1 = walk1_once;  // (shadow the set-up's: see above)
-      const auto& walk2 = walk2_once;
-#include "mlp_wide_eval.inc"
-      if (mode == 0) {  // the weight, H0 and the first (clamped) force, all from this evaluation at the held state
-        const float e0 = base_energy(xr);
-        const float term = db * (e0 - energy);
-        const float y = term - lw_c;
-        const float s = lw + y;
-        lw_c = (__builtin_fabsf(s) < __builtin_inff()) ? (s - lw) - y : 0.0f;  // an infinite sum stays what a plain sum gives
-        lw = s;
-        h0 = clamp_nanprop(b0 * e0 + beta_t * energy, -1e10f, 1e10f) + kinetic(p);
-#pragma unroll
-        for (int td = 0; td < DT; ++td)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) f[td][r] = clamp_nanprop(-(c0 * xr[td][r] + beta_t * g[td][r]), -1e6f, 1e6f);
-        e_last = energy;
-        mode = 1;
-        ++done;
-      } else if (mode == 1) {
-        // dU/dx at the proposal's position (f is free between the kick above and the force below).  The fast path needs it
-        // finite in every chain of the wave: then x is finite wherever (1 - b) is not zero, and a finite E vouches for x as in
-        // mlp_wide_hmc_body.h.  Decided per WAVE because the literal path re-runs the MFMA evaluation.
-        float gz = 0.0f;
-#pragma unroll
-        for (int td = 0; td < DT; ++td)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const float gm = c0 * xr[td][r] + beta_t * g[td][r];
-            f[td][r] = gm;
-            gz = __builtin_fmaf(gm, 0.0f, gz);
-          }
-        const bool all_fine = (bool)__all((__builtin_fabsf(energy) < __builtin_inff()) && gz == 0.0f);
-        if (all_fine) {
-          float pz = 0.0f;
-#pragma unroll
-          for (int td = 0; td < DT; ++td)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const float fn = __builtin_amdgcn_fmed3f(-f[td][r], -1e6f, 1e6f);
-              const float pn = __builtin_fmaf(half_eps, fn, p[td][r]);
-              f[td][r] = fn;
-              p[td][r] = pn;
-              pz = __builtin_fmaf(pn, 0.0f, pz);
-            }
-          if (pz != pz) {  // momentum overflow: x is finite, so f stands
-#pragma unroll
-            for (int td = 0; td < DT; ++td)
-#pragma unroll
-              for (int r = 0; r < 16; ++r) p[td][r] = nan_to_num0(p[td][r]);
-          }
-          e_last = energy;
-          ++done;
-        } else {  // literal semantics: NaN-propagating clamp, scrub, then re-evaluate on the scrubbed x
-#pragma unroll
-          for (int td = 0; td < DT; ++td)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const float fn = clamp_nanprop(-f[td][r], -1e6f, 1e6f);
-              p[td][r] = nan_to_num0(__builtin_fmaf(half_eps, fn, p[td][r]));
-              xr[td][r] = nan_to_num0(xr[td][r]);
-            }
-          mode = 2;
-        }
-      } else {  // mode 2: force and energy on the scrubbed position
-#pragma unroll
-        for (int td = 0; td < DT; ++td)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) f[td][r] = clamp_nanprop(-(c0 * xr[td][r] + beta_t * g[td][r]), -1e6f, 1e6f);
-        e_last = energy;
-        mode = 1;
-        ++done;
-      }
-    }
+    float xr[DT][16];
+    load_rows(lanes, xr, a.x, smp);
+    // dU/dx = (1 - b) inv_var0 x + b dE/dx
+    const auto leapfrog_grad = [&](int td, int r, float gr) __attribute__((always_inline)) { return c0 * xr[td][r] + beta_t * gr; };
+    // the evaluation at the held state: the weight, then H0
+    const auto leapfrog_held = [&](float energy) __attribute__((always_inline)) {
+      const float e0 = base_energy(xr);
+      const float term = db * (e0 - energy);
+      const float y = term - lw_c;
+      const float s = lw + y;
+      lw_c = (__builtin_fabsf(s) < __builtin_inff()) ? (s - lw) - y : 0.0f;  // an infinite sum stays what a plain sum gives
+      lw = s;
+      return clamp_nanprop(b0 * e0 + beta_t * energy, -1e10f, 1e10f) + kinetic_plain<DT>(p);
+    };
+#include "mlp_wide_leapfrog.inc"
     // U at the proposal: xr is the position e_last was evaluated at on either path
-    const float h1 = clamp_nanprop(b0 * base_energy(xr) + beta_t * e_last, -1e10f, 1e10f) + kinetic(p);
+    const float h1 = clamp_nanprop(b0 * base_energy(xr) + beta_t * e_last, -1e10f, 1e10f) + kinetic_plain<DT>(p);
 
     // ---- Metropolis accept
     const float dlt = clamp_nanprop(h0 - h1, -50.0f, 50.0f);
@@ -282,30 +172,10 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_ais_chain(WideAisArgs a) {
   if (active && h == 0) a.logw[sample] = lw;
 }
 
-template <int HT, int DT>
-int launch_ais_variant(const WideAisArgs& a, hipStream_t st, const char* who) {
-  constexpr int MODE = wide_mode(HT, DT);
-  const size_t smem = wide_smem_bytes(HT, DT, MODE);
-  static DeviceOnce attr_once;  // the LDS opt-in is a per-device function attribute
-  if (attr_once.first()) {  // > 64 KiB of dynamic LDS needs the opt-in
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_wide_ais_chain<HT, DT, MODE>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  }
-  const int64_t blocks = ceil_div64(a.n_chains, 32 * (kBlock / 64));
-  if (blocks > 0x7fffffffLL) return fail(EBM_EINVAL, "%s: too many chains for one launch", who);
-  hipLaunchKernelGGL((mlp_wide_ais_chain<HT, DT, MODE>), dim3((unsigned)blocks), dim3(kBlock), smem, st, a);
-  return check_launch(who);
-}
-
-template <int HT>
-int launch_ais_hidden(const WideAisArgs& a, hipStream_t st, const char* who) {
-  switch ((a.dim + 31) / 32) {
-    case 1: return launch_ais_variant<HT, 1>(a, st, who);
-    case 2: return launch_ais_variant<HT, 2>(a, st, who);
-    case 3: return launch_ais_variant<HT, 3>(a, st, who);
-    default: return launch_ais_variant<HT, 4>(a, st, who);
-  }
-}
+struct AisWalk {  // (launch_walk_by_dim, mlp_wide_rows.h)
+  template <int HT, int DT, int MODE>
+  static constexpr auto kernel = &mlp_wide_ais_chain<HT, DT, MODE>;
+};
 
 }  // namespace widemlp
 }  // namespace ebm

@@ -4,7 +4,7 @@
 namespace ebm {
 
 int launch_ais_mlp_wide_h128(const widemlp::WideAisArgs& a, hipStream_t st, const char* who) {
-  return widemlp::launch_ais_hidden<4>(a, st, who);
+  return widemlp::launch_walk_by_dim<widemlp::AisWalk, 4>(a, st, who);
 }
 
 }  // namespace ebm

@@ -31,7 +31,7 @@ int ghmc_mlp_chain_launch(const GhmcChainReq& q, hipStream_t st) {
   a.traj = q.traj; a.accept_mask = q.accept_mask; a.noise = q.noise; a.u = q.u;
   a.key = q.key(); a.step0 = q.offset;
   a.params = q.e.dev0;
-  if (q.e.n_comp == 64) return widemlp::launch_ghmc_hidden<2>(a, st, who);
+  if (q.e.n_comp == 64) return widemlp::launch_walk_by_dim<widemlp::GhmcWalk, 2>(a, st, who);
   return launch_ghmc_mlp_wide_h128(a, st, who);
 }
 

@@ -4,7 +4,7 @@
 namespace ebm {
 
 int launch_ghmc_mlp_wide_h128(const widemlp::WideGhmcArgs& a, hipStream_t st, const char* who) {
-  return widemlp::launch_ghmc_hidden<4>(a, st, who);
+  return widemlp::launch_walk_by_dim<widemlp::GhmcWalk, 4>(a, st, who);
 }
 
 }  // namespace ebm

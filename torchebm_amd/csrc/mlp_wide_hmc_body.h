@@ -1,8 +1,10 @@
 // Kernel body of the wide-MLP HMC transition kernel: see mlp_wide_hmc.hip.  Four translation units instantiate it (compiled in
 // parallel): mlp_wide_hmc.hip / mlp_wide_hmc_diag.hip (H = 64, 128; scalar or identity / diagonal mass) and
-// mlp_stream_hmc.hip / mlp_stream_hmc_diag.hip (H = 256).
+// mlp_stream_hmc.hip / mlp_stream_hmc_diag.hip (H = 256).  Rows, the plain-evaluation preamble and the launch are
+// mlp_wide_rows.h's.  The mode 0 / 1 / 2 loop is the machine of mlp_wide_leapfrog.inc, spelled here because it differs by the mass
+// coefficient of the drift, e_start, no gradient test and the workgroup-wide vote of SLAB -- and these tuned kernels keep their code.
 #pragma once
-#include "mlp_wide_body.h"
+#include "mlp_wide_rows.h"
 
 namespace ebm {
 namespace widemlp {
@@ -37,24 +39,11 @@ template <int HT, int DT, int MODE, bool DIAGM, bool FAST = false>
 __global__ __launch_bounds__(kBlock, 1) void mlp_wide_hmc_kernel(WideHmcArgs a) {
   constexpr bool EVAL_SCALED = false;  // (the chain kernel's THIN calls only: mlp_wide_body.h)
 #include "mlp_wide_setup.inc"
+  EBM_WIDE_WALKS_ONCE_SETUPS();  // (mlp_wide_rows.h)
+  EBM_WIDE_LANES();
 
-  // The accepted position stays in a.x (in/out): read at the top of a transition, written back by the chains that
+  // The accepted position stays in a.x (in/out): read at the top of a transition (load_rows), written back by the chains that
   // accept -- 16 DT registers fewer than carrying it, for one pass over the state per L + 1 evaluations.
-  auto load_state = [&](float (&dst)[DT][16], int64_t row) {
-#pragma unroll
-    for (int td = 0; td < DT; ++td)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int c0 = 32 * td + 8 * q + 4 * h;
-        if (quads && active && c0 + 3 < dim) {
-          const float4 v = *reinterpret_cast<const float4*>(a.x + row * dim + c0);
-          dst[td][4 * q] = v.x; dst[td][4 * q + 1] = v.y; dst[td][4 * q + 2] = v.z; dst[td][4 * q + 3] = v.w;
-        } else {
-#pragma unroll
-          for (int i = 0; i < 4; ++i) dst[td][4 * q + i] = (active && c0 + i < dim) ? a.x[row * dim + c0 + i] : 0.0f;
-        }
-      }
-  };
   const bool has_mass = a.mass_kind != EBM_MASS_NONE;
   // diagonal mass: per coordinate from the (L2-resident) vector where it is used; 1 beyond dim
   auto mass_at = [&](int td, int r) -> float {
@@ -150,7 +139,7 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_hmc_kernel(WideHmcArgs a) 
     const float em_s = has_mass ? eps / a.mass_safe : eps;
 
     float xr[DT][16], f[DT][16];
-    load_state(xr, smp);
+    load_rows(lanes, xr, a.x, smp);
 #pragma unroll
     for (int td = 0; td < DT; ++td)
 #pragma unroll
@@ -171,13 +160,8 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_hmc_kernel(WideHmcArgs a) 
             xr[td][r] = (32 * td + row_of(r, h) < dim) ? xn : 0.0f;
           }
       }
-      constexpr bool eval_energy_only = false, eval_block_cuts = false, eval_store_acts = false, eval_need_energy = true, eval_pin = false;
-      [[maybe_unused]] float* const act_base = nullptr;
-      [[maybe_unused]] constexpr uint32_t act_lane = 0;
-      [[maybe_unused]] constexpr float act_seed = 1.0f;
-      [[maybe_unused]] const auto eval_aux = [](auto) __attribute__((always_inline)) {};  // (nothing to hide in the tails' empty gaps)
-      [[maybe_unused]] constexpr bool slab_more = true;  // MODE 3: every evaluation asks for the next one's first slab (drained at the end)
-#include "mlp_wide_eval.inc"
+      constexpr bool eval_need_energy = true;
+#include "mlp_wide_plain_eval.inc"
       if (mode == 0) {  // H0 and the first (clamped) force
         h0 = clamp_nanprop(energy, -1e10f, 1e10f) + kinetic(p);
 #pragma unroll
@@ -246,7 +230,7 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_hmc_kernel(WideHmcArgs a) 
     if (!FAST && a.u) uu = active ? a.u[(int64_t)tr * a.n_chains + smp] : 2.0f;
     else uu = u01_half_open(pick(philox_at(a.key, (uint64_t)smp >> 2, a.step0 + 2ull * (uint64_t)tr + 1ull), (int)(smp & 3)));
     const bool accept = active && (uu < acc_p);
-    if (accept) {
+    if (accept) {  // (store_rows of mlp_wide_rows.h, spelled out: through the helper 4 of the 8 general kernels get another schedule)
 #pragma unroll
       for (int td = 0; td < DT; ++td)
 #pragma unroll
@@ -263,7 +247,7 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_hmc_kernel(WideHmcArgs a) 
     }
     if ((a.traj || (!FAST && a.diag_partials)) && --until_keep == 0) {
       until_keep = a.thin;
-      if (active && !accept) load_state(xr, smp);  // a rejected chain records the position it stays at
+      if (active && !accept) load_rows(lanes, xr, a.x, smp);  // a rejected chain records the position it stays at
       if (!FAST && a.diag_partials) {  // hmc.py:294-310: statistics of the state after the accept step, its (clamped) energy, the accept rate
         const int64_t wave_id = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
         const int kept = (int)(keep_off / dim);
@@ -271,16 +255,7 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_hmc_kernel(WideHmcArgs a) 
         wave_record_tail(a.diag_partials, a.diag_blocks, kept, wave_id, dim, clamp_nanprop(accept ? e_last : e_start, -1e10f, 1e10f),
                          active, accept, lane);
       }
-      if (a.traj && active) {
-        float* dst = a.traj + smp * (int64_t)a.n_kept * dim + keep_off;
-#pragma unroll
-        for (int td = 0; td < DT; ++td)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int c = 32 * td + row_of(r, h);
-            if (c < dim) dst[c] = xr[td][r];
-          }
-      }
+      if (a.traj && active) store_rows(lanes, a.traj + smp * (int64_t)a.n_kept * dim + keep_off, 0, xr);
       keep_off += dim;
     }
   }
@@ -291,18 +266,9 @@ template <int HT, int DT, bool DIAGM, bool FAST, int MODE_ = -1>
 int launch_hmc_variant(const WideHmcArgs& a, hipStream_t st, const char* who) {
   constexpr int MODE = MODE_ >= 0 ? MODE_ : wide_mode(HT, DT);
   constexpr bool STREAM = MODE == 1;
-  const size_t smem = wide_smem_bytes(HT, DT, MODE);
   if (STREAM && (reinterpret_cast<uintptr_t>(a.params) & 15) != 0)
     return fail(EBM_EINVAL, "%s: the MLP parameter block must be 16-byte aligned", who);
-  static DeviceOnce attr_once;  // the LDS opt-in is a per-device function attribute
-  if (attr_once.first()) {  // > 64 KiB of dynamic LDS needs the opt-in
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_wide_hmc_kernel<HT, DT, MODE, DIAGM, FAST>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-  }
-  const int64_t blocks = ceil_div64(a.n_chains, 32 * (kBlock / 64));
-  if (blocks > 0x7fffffffLL) return fail(EBM_EINVAL, "%s: too many chains for one launch", who);
-  hipLaunchKernelGGL((mlp_wide_hmc_kernel<HT, DT, MODE, DIAGM, FAST>), dim3((unsigned)blocks), dim3(kBlock), smem, st, a);
-  return check_launch(who);
+  return launch_walk<&mlp_wide_hmc_kernel<HT, DT, MODE, DIAGM, FAST>, HT, DT, MODE>(a, st, who);
 }
 
 // the FAST instantiations live in mlp_wide_hmc_fast.hip

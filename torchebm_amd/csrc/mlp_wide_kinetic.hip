@@ -31,7 +31,7 @@ int kinetic_mlp_chain_launch(const KineticChainReq& q, hipStream_t st) {
   a.traj = q.traj; a.noise = q.noise;
   a.key = q.key(); a.step0 = q.offset;
   a.params = q.e.dev0;
-  if (q.e.n_comp == 64) return widemlp::launch_kinetic_hidden<2>(a, st, who);
+  if (q.e.n_comp == 64) return widemlp::launch_walk_by_dim<widemlp::KineticWalk, 2>(a, st, who);
   return launch_kinetic_mlp_wide_h128(a, st, who);
 }
 

@@ -4,7 +4,7 @@
 namespace ebm {
 
 int launch_kinetic_mlp_wide_h128(const widemlp::WideKineticArgs& a, hipStream_t st, const char* who) {
-  return widemlp::launch_kinetic_hidden<4>(a, st, who);
+  return widemlp::launch_walk_by_dim<widemlp::KineticWalk, 4>(a, st, who);
 }
 
 }  // namespace ebm

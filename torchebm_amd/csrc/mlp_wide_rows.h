@@ -1,0 +1,151 @@
+// What the walks on the wide MLP energy share besides the evaluation (docs/design/mlp_wide.md, "Shared code of the walks"):
+// the lane-layout helpers -- rows of a [.., dim] matrix to and from the 32x32 C/D layout, the normal field a register quad at a
+// time, the plain kinetic energy --, the macros that go with the plain evaluation (mlp_wide_plain_eval.inc) and the host launcher.
+// Users: mlp_wide_hmc_body.h, mlp_wide_ais_body.h, mlp_wide_kinetic_body.h, mlp_wide_ghmc_body.h; the leapfrog state machine
+// of the AIS and GHMC walks is text of its own, mlp_wide_leapfrog.inc.  How a helper is spelled and called decides registers
+// and schedule of kernels at the register limit; where a body keeps a block in its own words, it says what the helper cost.
+#pragma once
+#include <type_traits>
+#include "mlp_wide_body.h"
+
+namespace ebm {
+namespace widemlp {
+
+// The lane geometry of mlp_wide_setup.inc and the lane's K-half, all four by REFERENCE to the kernel's own variables
+// (EBM_WIDE_LANES() behind the set-up).  This is not a neutral spelling.  Measured on the kinetic H = 64 unit: by reference the
+// four kernels are the hand-inlined lambdas' instruction for instruction; with dim / quads / active copied into the struct three
+// of them take 8, 3 and 2 more VGPRs; with the K-half passed to the helpers by value three of them come out with another
+// schedule (62 460 -> 62 869 lines of disassembly).  A walk that keeps an opaque copy of its K-half inside its step loop
+// (mlp_wide_kinetic_body.h says why) binds a second Lanes to that copy there.
+struct Lanes {
+  const int& dim;
+  const bool& quads;   // a register quad r = 4q .. 4q+3 is four consecutive, 16-byte aligned columns
+  const bool& active;  // the lane's chain exists
+  const int& h;        // the lane's K-half
+};
+#define EBM_WIDE_LANES() const Lanes lanes{dim, quads, active, h}
+
+// rows of a [.., dim] matrix into the C/D layout, zero beyond dim and for the lanes past the last chain
+template <int DT>
+__device__ __forceinline__ void load_rows(const Lanes& L, float (&dst)[DT][16], const float* src, int64_t row) {
+  const int hq = L.h;
+#pragma unroll
+  for (int td = 0; td < DT; ++td)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int c0 = 32 * td + 8 * q + 4 * hq;
+      if (L.quads && L.active && c0 + 3 < L.dim) {
+        const float4 w = *reinterpret_cast<const float4*>(src + row * L.dim + c0);
+        dst[td][4 * q] = w.x; dst[td][4 * q + 1] = w.y; dst[td][4 * q + 2] = w.z; dst[td][4 * q + 3] = w.w;
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) dst[td][4 * q + i] = (L.active && c0 + i < L.dim) ? src[row * L.dim + c0 + i] : 0.0f;
+      }
+    }
+}
+
+// ... and back (callers guard with `active`; columns past dim never reach memory)
+template <int DT>
+__device__ __forceinline__ void store_rows(const Lanes& L, float* dst, int64_t row, const float (&src)[DT][16]) {
+  const int hq = L.h;
+#pragma unroll
+  for (int td = 0; td < DT; ++td)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const int c = 32 * td + row_of(r, hq);
+      if (c < L.dim) dst[row * L.dim + c] = src[td][r];
+    }
+}
+
+// one register quad of the normal field at `step`, element chain * dim + col (zero beyond dim): one Philox counter where a
+// quad is four aligned columns, per element otherwise
+__device__ __forceinline__ void normal_quad(const Lanes& L, float (&z)[4], RngKey key, int c0, int64_t row, uint64_t step) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) z[i] = 0.0f;
+  if (c0 < L.dim) {
+    if (L.quads) {
+      const F4 nrm = normal4_at(key, ((uint64_t)row * (uint64_t)L.dim + (uint64_t)c0) >> 2, step);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) z[i] = nrm.v[i];
+    } else {
+      uint64_t have = ~0ull;
+      F4 nrm;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const uint64_t e = (uint64_t)row * (uint64_t)L.dim + (uint64_t)(c0 + i);
+        if ((e >> 2) != have) {
+          have = e >> 2;
+          nrm = normal4_at(key, have, step);
+        }
+        const int w = (int)(e & 3);
+        z[i] = w == 0 ? nrm.v[0] : (w == 1 ? nrm.v[1] : (w == 2 ? nrm.v[2] : nrm.v[3]));
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) z[i] = (c0 + i < L.dim) ? z[i] : 0.0f;
+}
+
+// sum q^2 over the whole chain (both K-halves; the padding registers are zero)
+template <int DT>
+__device__ __forceinline__ float sum_squares(const float (&q)[DT][16]) {
+  float acc = 0.0f;
+#pragma unroll
+  for (int td = 0; td < DT; ++td)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc += q[td][r] * q[td][r];
+  acc += __shfl_xor(acc, 32);
+  return acc;
+}
+// 0.5 p^T p, clamped to [0, 1e10]
+template <int DT>
+__device__ __forceinline__ float kinetic_plain(const float (&q)[DT][16]) {
+  return clamp_nanprop(0.5f * sum_squares<DT>(q), 0.0f, 1e10f);
+}
+
+// The plain evaluation (mlp_wide_plain_eval.inc) reads the images through walk1_once / walk2_once.  Behind the set-up a walk
+// says which they are.  OPAQUE: the images' LDS addresses formed once, an opaque scalar each -- left visible, the conversion of
+// the LDS pointer is re-derived at its uses inside the evaluation when registers run out (first met in the AIS kernel at H = 128
+// and two state tiles), in a form the backend rejects.  SETUPS: the set-up's own walks under that name, for the HMC kernels,
+// which were tuned without the trick and keep their code.
+#define EBM_WIDE_WALKS_ONCE_OPAQUE() \
+  auto walk1_once = walk1;           \
+  auto walk2_once = walk2;           \
+  asm volatile("" : "+s"(walk1_once.base), "+s"(walk2_once.base))
+#define EBM_WIDE_WALKS_ONCE_SETUPS() \
+  const auto& walk1_once = walk1;    \
+  const auto& walk2_once = walk2
+
+// One launch of KERNEL, an instantiation of a walk kernel at (HT, DT, MODE) that takes Args by value: the per-device LDS opt-in,
+// one wave per 32 chains, the launch.
+template <auto KERNEL, int HT, int DT, int MODE, class Args>
+int launch_walk(const Args& a, hipStream_t st, const char* who) {
+  const size_t smem = wide_smem_bytes(HT, DT, MODE);
+  static DeviceOnce attr_once;  // the LDS opt-in is a per-device function attribute
+  if (attr_once.first()) {  // > 64 KiB of dynamic LDS needs the opt-in
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+  }
+  const int64_t blocks = ceil_div64(a.n_chains, 32 * (kBlock / 64));
+  if (blocks > 0x7fffffffLL) return fail(EBM_EINVAL, "%s: too many chains for one launch", who);
+  hipLaunchKernelGGL(KERNEL, dim3((unsigned)blocks), dim3(kBlock), smem, st, a);
+  return check_launch(who);
+}
+
+// ... of the kernel for a.dim among a family's at hidden width 32 HT, each at wide_mode(HT, DT).  WALK names the family:
+//   template <int HT, int DT, int MODE> static constexpr auto kernel = &the_kernel<HT, DT, MODE>;
+template <class WALK, int HT, class Args>
+int launch_walk_by_dim(const Args& a, hipStream_t st, const char* who) {
+  const auto at = [&](auto dt) {
+    constexpr int DT = decltype(dt)::value, MODE = wide_mode(HT, DT);
+    return launch_walk<WALK::template kernel<HT, DT, MODE>, HT, DT, MODE>(a, st, who);
+  };
+  switch ((a.dim + 31) / 32) {
+    case 1: return at(std::integral_constant<int, 1>{});
+    case 2: return at(std::integral_constant<int, 2>{});
+    case 3: return at(std::integral_constant<int, 3>{});
+    default: return at(std::integral_constant<int, 4>{});
+  }
+}
+
+}  // namespace widemlp
+}  // namespace ebm
