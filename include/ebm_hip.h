@@ -396,6 +396,58 @@ EBM_API int ebm_tempering_hmc_chain_f32(const ebm_energy_t* energy, float* x, in
                                         const float* u_accept, const float* u_swap, uint64_t seed, uint64_t step0, void* stream);
 
 /*
+ * Replica-exchange HMC on the MLP energy: the algorithm, the parameter list, the slot matrix (row c * R + r, slot 0 the target),
+ * the Philox coordinates, the outputs and the counters of ebm_tempering_hmc_chain_f32 for EBM_ENERGY_MLP -- n_mh transitions of
+ * every slot and the swap events between them in ONE launch around the matrix-core evaluation (an addition to ABI 9: nothing else
+ * moved; ebm_tempering_hmc_chain_f32 keeps refusing the MLP).  docs/design/tempering_hmc_mlp.md.
+ *
+ * Transition t (0 .. n_mh - 1), every slot r of every ladder c:
+ *     w  = sqrt_temp[r] * z                 z: the normal field at step step0 + 3 t, element (c * R + r) * dim + col
+ *     E0, g = the evaluation at the held x;  f = clamp(-g, +-1e6);  H0 = clamp(E0, +-1e10) + clamp(0.5 sum w^2, 0, 1e10)
+ *     n_leapfrog times:  w = fma(eps[r] / 2, f, w);  x' = fma(eps[r], w, x');  E', g' = the evaluation at x';
+ *                        f = clamp(-g', +-1e6);  w = fma(eps[r] / 2, f, w)     -- the two half kicks are never merged
+ *         (where E' or g' is not finite in some row of the wave: the NaN-propagating clamp, w and x' scrubbed with
+ *          nan_to_num(nan = 0), and E', f re-evaluated on the scrubbed x' -- the literal safe-mode step, as in
+ *          ebm_ghmc_mlp_chain_f32)
+ *     H1 = clamp(E1, +-1e10) + clamp(0.5 sum w^2, 0, 1e10),  E1 = E' of the last step
+ *     d  = clamp(beta[r] * (H0 - H1), +-50);  accepted iff u < min(1, exp d)   u: the uniform field at step step0 + 3 t + 1,
+ *                                                                              element c * R + r; a NaN rejects
+ *     e_now = accepted ? E1 : E0            raw fp32, not clamped: the energy of the state the slot now holds
+ * A transition makes n_leapfrog + 1 evaluations and carries no energy, force or momentum to the next one; x lives in the
+ * caller's buffer between transitions.
+ *
+ * Swap event m = (t + 1) / swap_every - 1 after transition t when (t + 1) % swap_every == 0: even events pair (0,1), (2,3), ..,
+ * odd events (1,2), (3,4), ..; delta = (beta[r] - beta[r + 1]) * (e_now[r] - e_now[r + 1]); the pair swaps iff delta == delta and
+ * u < exp(min(delta, 0)), u the uniform field at step step0 + 3 t + 2, element c * R + r, the lower slot's row.  An event
+ * evaluates nothing.  A swap exchanges the two STATES (rows c * R + r and c * R + r + 1 of x).
+ *
+ * Outputs and draws: after the event, when (t + 1) % thin == 0, slot 0's state goes to traj[c, (t + 1) / thin - 1]
+ * (traj: [n_ladders, n_mh / thin, dim] or NULL); accept_mask: NULL or uint8[n_mh, n_ladders * R] by slot row; accept_counts: NULL
+ * or device uint32[R], swap_counts: NULL or device uint32[2 (R - 1)] (attempts of pair (p, p + 1) at p, accepts at R - 1 + p),
+ * both ADDED to, once per workgroup at the end of the call; p_noise[n_mh, n_ladders * R, dim] / u_accept[n_mh, n_ladders * R] /
+ * u_swap[n_mh / swap_every, n_ladders * R]: all three NULL or all three given.  The call owns the Philox steps
+ * step0 .. step0 + 3 n_mh - 1.  Columns past dim and rows past n_ladders * R never reach memory; 64-bit row indices.
+ *
+ * Two calls equal one whenever the first holds an even number of events (m restarts at 0 in every call): (n1, step0) then
+ * (n2, step0 + 3 n1) with n1 % (2 swap_every) == 0 gives the bits of one call of n1 + n2.  With sqrt_temp = beta = 1 in every
+ * slot, one eps and no event the rows are ebm_ghmc_mlp_chain_f32 chains at gamma = inf on the same draws.
+ *
+ * The evaluation is three-way split bf16 (or exact-f32 MFMA) arithmetic with fp32 accumulation: fp32 accuracy, not autograd's
+ * rounding.
+ *
+ * Refusals, all in front of any device access and of the early return for n_ladders == 0: a NULL energy, x, eps, sqrt_temp or
+ * beta; n_mh, n_leapfrog, thin or swap_every below 1; n_ladders < 0; draws given in part; x, traj or p_noise not 16-byte aligned
+ * (EBM_EINVAL); a kind other than EBM_ENERGY_MLP (EBM_EKIND); a hidden width (energy->n_comp) other than 64 / 128, dim outside
+ * 1 .. 128 or n_replicas not in {2, 4, 8, 16, 32} (EBM_EDIM, the message names the three numbers).  No H = 256, no pre-split W1
+ * image (energy->aux is ignored), no tables, no mass matrix, no diagnostics records.
+ */
+EBM_API int ebm_tempering_hmc_mlp_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_ladders, int32_t n_replicas, int32_t dim,
+                                            int32_t n_mh, int32_t n_leapfrog, const float* eps, const float* sqrt_temp,
+                                            const float* beta, int32_t swap_every, int32_t thin, float* traj, uint8_t* accept_mask,
+                                            uint32_t* accept_counts, uint32_t* swap_counts, const float* p_noise,
+                                            const float* u_accept, const float* u_swap, uint64_t seed, uint64_t step0, void* stream);
+
+/*
  * Annealed importance sampling (Neal 2001): every chain walks ONE state from the base N(0, sigma0^2 I) to the target through
  * n_temps tempered laws and accumulates the importance weight whose mean estimates Z / Z_0 -- the whole walk in ONE launch (an
  * addition to ABI 9: nothing else moved).  The third member of the tempered family: the replica-exchange entries run R

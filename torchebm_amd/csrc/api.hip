@@ -452,6 +452,33 @@ int ebm_tempering_hmc_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_
   return tempering_hmc_chain_launch(q, (hipStream_t)stream);
 }
 
+int ebm_tempering_hmc_mlp_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_ladders, int32_t n_replicas, int32_t dim,
+                                    int32_t n_mh, int32_t n_leapfrog, const float* eps, const float* sqrt_temp, const float* beta,
+                                    int32_t swap_every, int32_t thin, float* traj, uint8_t* accept_mask, uint32_t* accept_counts,
+                                    uint32_t* swap_counts, const float* p_noise, const float* u_accept, const float* u_swap,
+                                    uint64_t seed, uint64_t step0, void* stream) {
+  const char* who = "ebm_tempering_hmc_mlp_chain_f32";
+  if (int r = check_energy(energy, dim, who)) return r;
+  if (energy->kind != EBM_ENERGY_MLP)
+    return fail(EBM_EKIND, "%s: this entry walks the MLP energy only (ebm_tempering_hmc_chain_f32 takes the analytic kinds)", who);
+  // (the dim range and the ladder lengths are tempering_hmc_mlp_check_shape's to refuse)
+  if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
+  if (!eps || !sqrt_temp || !beta) return fail(EBM_EINVAL, "%s: eps / sqrt_temp / beta is NULL", who);
+  if (n_ladders < 0) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d, %d]", who, (long long)n_ladders, n_replicas, dim);
+  if (n_mh < 1 || n_leapfrog < 1 || swap_every < 1 || thin < 1)
+    return fail(EBM_EINVAL, "%s: n_mh=%d n_leapfrog=%d swap_every=%d thin=%d (all must be >= 1)", who, n_mh, n_leapfrog, swap_every,
+                thin);
+  if ((p_noise == nullptr) != (u_accept == nullptr) || (p_noise == nullptr) != (u_swap == nullptr))
+    return fail(EBM_EINVAL, "%s: p_noise, u_accept and u_swap must be given together", who);
+  if (!aligned16(x) || (traj && !aligned16(traj)) || (p_noise && !aligned16(p_noise)))
+    return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  if (int r = tempering_hmc_mlp_check_shape(energy->n_comp, dim, n_replicas)) return r;
+  if (n_ladders == 0) return 0;
+  const TemperingHmcChainReq q{*energy, x, n_ladders, n_replicas, dim, n_mh, n_leapfrog, eps, sqrt_temp, beta, swap_every, thin,
+                               traj, accept_mask, accept_counts, swap_counts, p_noise, u_accept, u_swap, seed, step0};
+  return tempering_hmc_mlp_chain_launch(q, (hipStream_t)stream);
+}
+
 // Both annealed-importance-sampling entries: the analytic kinds on the lane-group kernel, the MLP energy on the matrix cores
 static int ais_chain_impl(const char* who, bool mlp, const ebm_energy_t* energy, float* x, float* logw, int64_t n_chains, int32_t dim,
                           int32_t n_temps, int32_t n_leapfrog, const float* beta, const float* eps, float sigma0, float inv_var0,

@@ -310,6 +310,10 @@ int tempering_check_geometry(int32_t n_replicas, int32_t dim);  // 0, or the ref
 // ---------------------------------------------------------------------------------
 int tempering_hmc_chain_launch(const TemperingHmcChainReq&, hipStream_t);
 int tempering_hmc_check_geometry(int32_t n_replicas, int32_t dim);  // 0, or the refusal (dim > 256, ladder wider than a workgroup)
+// ... on the MLP energy (mlp_wide_tempering.hip: the same request; 32 slot rows per wave around the matrix-core evaluation, n_leapfrog + 1 of them per transition, a swap moves the states between neighbouring lanes)
+int tempering_hmc_mlp_chain_launch(const TemperingHmcChainReq&, hipStream_t);
+// 0, or the refusal (hidden width not 64 / 128, dim outside 1 .. 128, n_replicas not in {2, 4, 8, 16, 32})
+int tempering_hmc_mlp_check_shape(int32_t hidden, int32_t dim, int32_t n_replicas);
 
 // ---------------------------------------------------------------------------------
 // Annealed importance sampling (ais.hip: one walker per chain through the temperatures in time, the weight from carried energies)

@@ -25,7 +25,8 @@ Replica-exchange HMC
 --------------------
 The same ladders with a Metropolis-corrected HMC transition in every slot, so no slot carries a discretisation bias: slot
 ``r`` samples ``exp(-E / T_r)`` exactly.  See :class:`ReplicaExchangeHMC`; the fused route is ONE launch of
-``ebm_tempering_hmc_chain_f32`` (docs/design/tempering_hmc.md).
+``ebm_tempering_hmc_chain_f32`` (docs/design/tempering_hmc.md) and, for an ``MLPEnergy`` with the opt-in
+``sampler.fused_mlp = True``, ONE launch of ``ebm_tempering_hmc_mlp_chain_f32`` (docs/design/tempering_hmc_mlp.md).
 """
 
 from __future__ import annotations
@@ -260,6 +261,11 @@ class ReplicaExchangeLangevin(_LadderSampler):
         return state, (traj if want_traj else None), diag
 
 
+#: the ladder lengths of ``ebm_tempering_hmc_mlp_chain_f32`` (whole ladders per 32-row wave) and its widest row
+FUSED_MLP_LADDERS = (2, 4, 8, 16, 32)
+FUSED_MLP_MAX_DIM = 128
+
+
 def hmc_ladder_coefficients(temperatures: Sequence[float]) -> Tuple[torch.Tensor, torch.Tensor]:
     """``(sqrt_temp[R], beta[R])`` as fp32: formed in double, rounded once (include/ebm_hip.h)."""
     t = torch.tensor([float(v) for v in temperatures], dtype=torch.float64)
@@ -291,7 +297,15 @@ class ReplicaExchangeHMC(_LadderSampler):
     constant step sizes, ``dim <= 256`` and a ladder that fits one workgroup (``R * G <= 256``): ONE launch of
     ``ebm_tempering_hmc_chain_f32`` per call, never a fallback; ``eager`` -- everything else, the same algorithm in torch
     ops, drawing ``randn(n, R, dim)`` and ``rand(n, R)`` per transition and ``rand(n, R)`` per event.
+
+    ``fused_mlp`` (class attribute, ``False``): set it on a sampler to send an eligible ``MLPEnergy`` call -- hidden width
+    64 / 128, ``dim == in_dim <= 128``, ``R`` in {2, 4, 8, 16, 32}, constant step sizes -- to the route ``fused_mlp``: ONE launch
+    of ``ebm_tempering_hmc_mlp_chain_f32`` per call with the same Philox coordinates, the matrix-core evaluation inside the
+    trajectories (fp32 accuracy, not autograd's rounding), never a fallback.  Off by default: a default sampler on an MLP keeps
+    its eager bits.
     """
+
+    fused_mlp = False
 
     def __init__(
         self,
@@ -341,7 +355,13 @@ class ReplicaExchangeHMC(_LadderSampler):
         if rows.shape[1] > 256:
             return "eager", None
         spec = fused_spec_for(self.model, rows, None)
-        if spec is None or spec.kind == _lib.ENERGY_MLP:
+        if spec is None:
+            return "eager", None
+        if spec.kind == _lib.ENERGY_MLP:
+            dim = rows.shape[1]
+            if (self.fused_mlp and self.n_replicas in FUSED_MLP_LADDERS and spec.n_comp in (64, 128)
+                    and dim == getattr(self.model, "in_dim", None) and dim <= FUSED_MLP_MAX_DIM):
+                return "fused_mlp", spec
             return "eager", None
         if self.n_replicas > 64 or self.n_replicas * lanes_per_row(rows.shape[1]) > 256:
             return "eager", None
@@ -373,6 +393,9 @@ class ReplicaExchangeHMC(_LadderSampler):
         route, spec = self._route(x)
         if route == "fused":
             state, traj, diag = self._sample_fused(x, spec, n_steps, thin, return_trajectory, return_diagnostics, generator)
+        elif route == "fused_mlp":
+            state, traj, diag = self._sample_fused(x, spec, n_steps, thin, return_trajectory, return_diagnostics, generator,
+                                                   entry="ebm_tempering_hmc_mlp_chain_f32")
         else:
             state, traj, diag = self._sample_eager(x, n_steps, thin, return_trajectory, return_diagnostics, generator)
         out = traj if return_trajectory else (state if return_replicas else state[:, 0].contiguous())
@@ -441,7 +464,7 @@ class ReplicaExchangeHMC(_LadderSampler):
         return x, traj, diag
 
     # ---------------------------------------------------------------------------------
-    # route: one launch of ebm_tempering_hmc_chain_f32
+    # routes: one launch of ebm_tempering_hmc_chain_f32, or (fused_mlp) of ebm_tempering_hmc_mlp_chain_f32 -- the same parameter list
     # ---------------------------------------------------------------------------------
     def _ladder_on(self, device: torch.device) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
         """The three device arrays of the ladder, kept for the next call with the same step sizes."""
@@ -454,7 +477,8 @@ class ReplicaExchangeHMC(_LadderSampler):
             self._ladder_cache = cached
         return cached[1], cached[2], cached[3]
 
-    def _sample_fused(self, x, spec: FusedSpec, n_steps, thin, want_traj, want_diag, generator):
+    def _sample_fused(self, x, spec: FusedSpec, n_steps, thin, want_traj, want_diag, generator,
+                      entry: str = "ebm_tempering_hmc_chain_f32"):
         n, R, dim = x.shape
         n_kept = n_steps // thin
         state = _lib.dense_f32(x).clone()  # the kernel updates in place; never the caller's tensor
@@ -469,7 +493,7 @@ class ReplicaExchangeHMC(_LadderSampler):
         spec_c = spec.to_c()
         if n > 0 and n_steps > 0:
             _lib.call(
-                "ebm_tempering_hmc_chain_f32",
+                entry,
                 spec_c, _lib.ptr(state), n, R, dim, n_steps, self.n_leapfrog_steps, _lib.ptr(eps), _lib.ptr(sqrt_temp), _lib.ptr(beta),
                 self.swap_every, thin, _lib.ptr(traj) if need_kept else None, None, _lib.ptr(accepts), _lib.ptr(swaps),
                 None, None, None, seed, step0, stream,
@@ -479,7 +503,11 @@ class ReplicaExchangeHMC(_LadderSampler):
         if want_diag:
             diag = new_outputs(state, (n, dim), n_kept, False, True)[1]
             if n > 0 and n_kept > 0:
-                kept_statistics(spec_c, traj, diag, stream)
+                if spec.kind == _lib.ENERGY_MLP:  # the kept states' statistics in torch ops, their energy the model's
+                    for keep in range(n_kept):
+                        record_kept(traj[:, keep], keep, None, diag, lambda x_: self._model_energy(x_.contiguous(), {}))
+                else:
+                    kept_statistics(spec_c, traj, diag, stream)
             c = (swaps.to(torch.int64) & 0xFFFFFFFF).to(torch.float64)
             diag["swap_acceptance"] = (c[R - 1 :] / c[: R - 1]).to(torch.float32)
             got = (accepts.to(torch.int64) & 0xFFFFFFFF).to(torch.float64)
