@@ -800,6 +800,60 @@ EBM_API int ebm_kinetic_moments_f32(const ebm_energy_t* energy, float* x, float*
                                     uint8_t* accept_mask, uint32_t* accept_count, const float* noise, const float* u,
                                     uint64_t seed, uint64_t offset, void* stream);
 
+/*
+ * Per-chain running moments on the MLP energy: the statistics of ebm_kinetic_moments_f32 above -- the same parameter list, the
+ * same counted states, recip table, Welford recurrences and layouts of mom, e_mom, v2_mom, traj, e_traj and v_traj -- around the
+ * walks of ebm_kinetic_mlp_chain_f32 (sampler = 0, step = h) and ebm_ghmc_mlp_chain_f32 (sampler = 1, step = eps), in ONE launch
+ * (an addition to ABI 9: nothing else moved; ebm_kinetic_moments_f32 still refuses the MLP).  One wave walks 32 chains.
+ *
+ * Walkers.  Those of the two plain MLP entries, operation for operation, with the constants formed by the same host code.
+ *   BAOAB: one evaluation site, k_steps + 1 evaluations; evaluation i closes step i - 1 (B) and opens step i (B A O A); the
+ *          kicks are never merged; the raw gradient; z_i the normal field at Philox step offset + 1 + i or noise[i].  A call owns
+ *          the steps offset .. offset + k_steps.
+ *   GHMC:  the O refresh stored back to v; n_leapfrog + 1 evaluations per transition through the safe-mode leapfrog; accepted iff
+ *          u < min(1, exp(clamp(beta (H0 - H1), +-50))); a reject flips the stored velocity; z_t at step offset + 1 + 2 t, the
+ *          uniform at offset + 2 + 2 t.  A call owns the steps offset .. offset + 2 k_steps.  gamma = +inf is the HMC transition.
+ *   draw_v0, noise and u as in the plain entries.  The final x, v and GHMC's accept mask are the plain entries' on the same draws.
+ *
+ * Counted states.  The first burn_in transitions are not counted; k_steps - burn_in == 2 h with h >= 2; a counted state is the
+ * state AFTER the transition; a GHMC reject counts the held state again.  Per coordinate, per half and with c = 1 .. h
+ *     d = x - mean;   mean = mean + d * recip[c - 1];   M2 = M2 + d * (x - mean)
+ * in fp32, every operation rounded on its own; mom is float[4][n_chains][dim] (mean_a, M2_a, mean_b, M2_b), e_mom NULL or
+ * float[4][n_chains].  BAOAB also keeps v2_mom, NULL or float[2][n_chains][dim]:  m = m + (v * v - m) * recip[c - 1]  with v the
+ * velocity at the END of the step (behind the closing B), and v_traj, NULL or float[n_chains][2 h][dim], those velocities.
+ * traj: NULL, or float[n_chains][2 h][dim], the counted positions; e_traj: NULL, or float[n_chains][2 h], their energies (written
+ * with or without e_mom).
+ *
+ * Energies add no evaluation.  BAOAB: evaluation i >= 1 is made at the position behind step i - 1, the counted state.  GHMC: E'
+ * of the proposal on an accept; on a reject the E of the held position that H0 was formed from.  The value counted is the
+ * unclamped one.
+ *
+ * Working storage.  The pairs do not live in registers: mom, e_mom and v2_mom are WORKING STORAGE during the launch -- each
+ * counted transition reads a chain's pair from them and writes it back (a lane reads only what it stored itself) -- and defined
+ * at return.  At c == 1 the pair starts from zero and the planes are not read: the caller need not initialise them, and whatever
+ * they held (a NaN included) never reaches the output.  They must not overlap each other or any other buffer of the call.
+ *
+ * accept_mask: NULL, or uint8[k_steps][n_chains] (GHMC); accept_count: NULL, or device uint32[k_steps] the call ADDS to (one
+ * atomic per wave and transition; GHMC).  Both are ignored for BAOAB, as n_leapfrog and u are.  Columns past dim and rows past
+ * n_chains never reach memory; 64-bit row indices.
+ *
+ * The evaluation is three-way split bf16 (or exact-f32 MFMA) arithmetic with fp32 accumulation: fp32 accuracy, not autograd's
+ * rounding.
+ *
+ * Refusals, all in front of any device access and of the early return for n_chains == 0.  EBM_EINVAL: a NULL energy, x, v, mom
+ * or recip; n_chains < 0; an unknown sampler; burn_in < 0 or k_steps - burn_in not 2 h with h >= 2; step, gamma or temperature
+ * not positive, or NaN (all finite for BAOAB; gamma = +inf allowed for GHMC); n_leapfrog < 1, a non-NULL v2_mom or a non-NULL
+ * v_traj for GHMC.  EBM_EKIND: a kind other than EBM_ENERGY_MLP.  EBM_EDIM: a hidden width (energy->n_comp) other than 64 / 128
+ * or dim outside 1 .. 128 (the message names both).  x, v, mom, v2_mom, traj, v_traj and noise must be 16-byte aligned.  No
+ * H = 256, no pre-split W1 image (energy->aux is ignored), no tables, no mass matrix.
+ */
+EBM_API int ebm_kinetic_moments_mlp_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim,
+                                        int32_t sampler, int32_t k_steps, int32_t burn_in, int32_t n_leapfrog, double step,
+                                        double gamma, double temperature, int32_t draw_v0, const float* recip, float* mom,
+                                        float* e_mom, float* v2_mom, float* traj, float* e_traj, float* v_traj,
+                                        uint8_t* accept_mask, uint32_t* accept_count, const float* noise, const float* u,
+                                        uint64_t seed, uint64_t offset, void* stream);
+
 /* The accept step with the RNG coordinates in DEVICE memory (rng_state = {seed, step}; the uniforms
  * are drawn at step rng_state[1] + step_delta): the graph-capturable form, see
  * ebm_langevin_step_dev_f32.  No injected-uniform form. */

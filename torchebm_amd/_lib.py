@@ -51,6 +51,7 @@ EXPORTS = (
     "ebm_ghmc_chain_f32",
     "ebm_ghmc_mlp_chain_f32",
     "ebm_kinetic_moments_f32",
+    "ebm_kinetic_moments_mlp_f32",
     "ebm_leapfrog_kick_drift_f32",
     "ebm_leapfrog_kick_f32",
     "ebm_hmc_accept_f32",
@@ -175,6 +176,11 @@ _PROTOTYPES = {
         [_ENERGY_P, _p, _p, _i64, _i32, _i32, _i32, _d, _d, _d, _i32, _i32, _p, _p, _p, _p, _u64, _u64, _p],
     ),
     "ebm_kinetic_moments_f32": (
+        C.c_int,
+        [_ENERGY_P, _p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _d, _d, _d, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
+         _u64, _u64, _p],
+    ),
+    "ebm_kinetic_moments_mlp_f32": (
         C.c_int,
         [_ENERGY_P, _p, _p, _i64, _i32, _i32, _i32, _i32, _i32, _d, _d, _d, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p,
          _u64, _u64, _p],

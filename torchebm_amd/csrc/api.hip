@@ -723,6 +723,53 @@ int ebm_kinetic_moments_f32(const ebm_energy_t* energy, float* x, float* v, int6
   return kinetic_moments_chain_launch(q, (hipStream_t)stream);
 }
 
+int ebm_kinetic_moments_mlp_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t sampler,
+                                int32_t k_steps, int32_t burn_in, int32_t n_leapfrog, double step, double gamma,
+                                double temperature, int32_t draw_v0, const float* recip, float* mom, float* e_mom, float* v2_mom,
+                                float* traj, float* e_traj, float* v_traj, uint8_t* accept_mask, uint32_t* accept_count,
+                                const float* noise, const float* u, uint64_t seed, uint64_t offset, void* stream) {
+  const char* who = "ebm_kinetic_moments_mlp_f32";
+  if (int r = check_energy(energy, dim, who)) return r;
+  if (energy->kind != EBM_ENERGY_MLP)
+    return fail(EBM_EKIND, "%s: this entry walks the MLP energy only (ebm_kinetic_moments_f32 takes the analytic kinds)", who);
+  // (the dim range is kinetic_moments_mlp_check_shape's to refuse)
+  if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
+  if (!v) return fail(EBM_EINVAL, "%s: velocity pointer is NULL", who);
+  if (n_chains < 0) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d]", who, (long long)n_chains, dim);
+  if (sampler != 0 && sampler != 1) return fail(EBM_EINVAL, "%s: sampler=%d (0 = BAOAB, 1 = GHMC)", who, sampler);
+  const bool ghmc = sampler == 1;
+  if (k_steps < 0 || burn_in < 0 || burn_in > k_steps || ((k_steps - burn_in) & 1) || (k_steps - burn_in) / 2 < 2)
+    return fail(EBM_EINVAL, "%s: k_steps=%d burn_in=%d (k_steps - burn_in must be 2 h with h >= 2)", who, k_steps, burn_in);
+  // (GHMC: gamma = +inf is allowed, a full refresh)
+  if (!(step > 0.0) || !(gamma > 0.0) || !(temperature > 0.0) || !std::isfinite(step) || !std::isfinite(temperature) ||
+      (!ghmc && !std::isfinite(gamma)))
+    return fail(EBM_EINVAL, "%s: step=%g gamma=%g temperature=%g (all must be positive; finite, but for GHMC's gamma)", who, step,
+                gamma, temperature);
+  if (ghmc && n_leapfrog < 1) return fail(EBM_EINVAL, "%s: n_leapfrog=%d", who, n_leapfrog);
+  if (ghmc && (v2_mom || v_traj)) return fail(EBM_EINVAL, "%s: v2_mom / v_traj are BAOAB outputs (sampler = 0)", who);
+  if (!recip || !mom) return fail(EBM_EINVAL, "%s: recip / mom is NULL", who);
+  if (int r = kinetic_moments_mlp_check_shape(energy->n_comp, dim)) return r;
+  if (n_chains == 0) return 0;
+  if (!aligned16(x) || !aligned16(v) || !aligned16(mom) || (v2_mom && !aligned16(v2_mom)) || (traj && !aligned16(traj)) ||
+      (v_traj && !aligned16(v_traj)) || (noise && !aligned16(noise)))
+    return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  // the walkers' constants by the host code of the two plain MLP entries
+  if (ghmc) {
+    const GhmcChainReq g = ghmc_request(energy, x, v, n_chains, dim, k_steps, n_leapfrog, step, gamma, temperature, draw_v0, 1,
+                                        nullptr, accept_mask, noise, u, seed, offset);
+    const KineticMomentsChainReq q{*energy, x, v, n_chains, dim, true, k_steps, burn_in, n_leapfrog, 0.0f, g.eps, g.c1, g.c2,
+                                   g.sqrt_temp, g.beta, draw_v0 != 0, recip, mom, e_mom, nullptr, traj, e_traj, nullptr,
+                                   accept_mask, accept_count, noise, u, seed, offset};
+    return kinetic_moments_mlp_chain_launch(q, (hipStream_t)stream);
+  }
+  const KineticChainReq b = kinetic_request(energy, x, v, n_chains, dim, k_steps, step, gamma, temperature, draw_v0, 1, nullptr,
+                                            noise, seed, offset);
+  const KineticMomentsChainReq q{*energy, x, v, n_chains, dim, false, k_steps, burn_in, n_leapfrog, b.hh, 0.0f, b.c1, b.c2,
+                                 b.sqrt_temp, 0.0f, draw_v0 != 0, recip, mom, e_mom, v2_mom, traj, e_traj, v_traj, nullptr, nullptr,
+                                 noise, nullptr, seed, offset};
+  return kinetic_moments_mlp_chain_launch(q, (hipStream_t)stream);
+}
+
 int ebm_leapfrog_kick_drift_f32(const float* x, const float* p, const float* force, float* x_new,
                                 float* p_half, int64_t n_chains, int32_t dim, float eps,
                                 int32_t mass_kind, double mass_scalar, const float* mass_diag,

@@ -354,5 +354,8 @@ int ghmc_mlp_check_shape(int32_t hidden, int32_t dim);  // 0, or the refusal (hi
 // ---------------------------------------------------------------------------------
 int kinetic_moments_chain_launch(const KineticMomentsChainReq&, hipStream_t);
 int kinetic_moments_check_geometry(int32_t dim);  // 0, or the refusal (dim outside 1 .. 256)
+// ... on the MLP energy (mlp_wide_kinetic_moments.hip, mlp_wide_ghmc_moments.hip: the same request; the walks of the two MLP entries above with the Welford pairs kept in the caller's planes, updated in place once per counted transition)
+int kinetic_moments_mlp_chain_launch(const KineticMomentsChainReq&, hipStream_t);
+int kinetic_moments_mlp_check_shape(int32_t hidden, int32_t dim);  // 0, or the refusal (hidden width not 64 / 128, dim outside 1 .. 128)
 
 }  // namespace ebm

@@ -1,0 +1,10 @@
+// The H = 128 instantiations of the wide-MLP generalized-HMC running-moments kernel -- see mlp_wide_kinetic_moments.hip.
+#include "mlp_wide_ghmc_moments_body.h"
+
+namespace ebm {
+
+int launch_ghmc_moments_mlp_wide_h128(const widemlp::WideGhmcMomentsArgs& a, hipStream_t st, const char* who) {
+  return widemlp::launch_walk_by_dim<widemlp::GhmcMomentsWalk, 4>(a, st, who);
+}
+
+}  // namespace ebm

@@ -1,7 +1,8 @@
 // What the walks on the wide MLP energy share besides the evaluation (docs/design/mlp_wide.md, "Shared code of the walks"):
 // the lane-layout helpers -- rows of a [.., dim] matrix to and from the 32x32 C/D layout, the normal field a register quad at a
 // time, the plain kinetic energy --, the macros that go with the plain evaluation (mlp_wide_plain_eval.inc) and the host launcher.
-// Users: mlp_wide_hmc_body.h, mlp_wide_ais_body.h, mlp_wide_kinetic_body.h, mlp_wide_ghmc_body.h; the leapfrog state machine
+// Users: mlp_wide_hmc_body.h, mlp_wide_ais_body.h, mlp_wide_kinetic_body.h, mlp_wide_ghmc_body.h and the two running-moments
+// bodies (mlp_wide_kinetic_moments_body.h, mlp_wide_ghmc_moments_body.h: moments_rows, moments_scalar); the leapfrog state machine
 // of the AIS and GHMC walks is text of its own, mlp_wide_leapfrog.inc.  How a helper is spelled and called decides registers
 // and schedule of kernels at the register limit; where a body keeps a block in its own words, it says what the helper cost.
 #pragma once
@@ -84,6 +85,84 @@ __device__ __forceinline__ void normal_quad(const Lanes& L, float (&z)[4], RngKe
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i) z[i] = (c0 + i < L.dim) ? z[i] : 0.0f;
+}
+
+// The running moments of a walk kept in the CALLER's planes (mlp_wide_kinetic_moments_body.h, mlp_wide_ghmc_moments_body.h;
+// docs/design/kinetic_moments_mlp.md): one in-place update of a row, a register quad at a time, so nothing of a plane lives in
+// registers through an evaluation.  A lane reads back only what it stored itself (the columns of load_rows / store_rows);
+// `first` (wave-uniform): the pair starts from zero and the planes are NOT read.  Every operation is rounded on its own (the
+// units compile with -ffp-contract=off).  VSQ == false, the Welford pair of q with rc = recip[c - 1]:
+//     d = q - mean;   mean = mean + d * rc;   M2 = M2 + d * (q - mean)
+// VSQ == true, the running mean of q^2 (m2 is not touched):   m = m + (q * q - m) * rc
+template <bool VSQ, int DT>
+__device__ __forceinline__ void moments_rows(const Lanes& L, float* mean, float* m2, int64_t row, const float (&q)[DT][16], float rc,
+                                             bool first) {
+  if (!L.active) return;
+  const int hq = L.h;
+#pragma unroll
+  for (int td = 0; td < DT; ++td)
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd) {
+      const int c0 = 32 * td + 8 * qd + 4 * hq;
+      float* const pm = mean + row * L.dim + c0;
+      float* const ps = m2 + row * L.dim + c0;
+      const bool whole = L.quads && c0 + 3 < L.dim;
+      float mu[4] = {0.0f, 0.0f, 0.0f, 0.0f}, s2[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      if (!first) {
+        if (whole) {
+          const float4 w = *reinterpret_cast<const float4*>(pm);
+          mu[0] = w.x; mu[1] = w.y; mu[2] = w.z; mu[3] = w.w;
+          if constexpr (!VSQ) {
+            const float4 y = *reinterpret_cast<const float4*>(ps);
+            s2[0] = y.x; s2[1] = y.y; s2[2] = y.z; s2[3] = y.w;
+          }
+        } else {
+#pragma unroll
+          for (int i = 0; i < 4; ++i)
+            if (c0 + i < L.dim) {
+              mu[i] = pm[i];
+              if constexpr (!VSQ) s2[i] = ps[i];
+            }
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const float qi = q[td][4 * qd + i];
+        if constexpr (VSQ) {
+          const float vv = qi * qi;
+          mu[i] = mu[i] + (vv - mu[i]) * rc;
+        } else {
+          const float d = qi - mu[i];
+          mu[i] = mu[i] + d * rc;
+          s2[i] = s2[i] + d * (qi - mu[i]);
+        }
+      }
+      if (whole) {
+        *reinterpret_cast<float4*>(pm) = make_float4(mu[0], mu[1], mu[2], mu[3]);
+        if constexpr (!VSQ) *reinterpret_cast<float4*>(ps) = make_float4(s2[0], s2[1], s2[2], s2[3]);
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (c0 + i < L.dim) {
+            pm[i] = mu[i];
+            if constexpr (!VSQ) ps[i] = s2[i];
+          }
+      }
+    }
+}
+// ... and of one number per chain (the energy), by the lane of K-half 0
+__device__ __forceinline__ void moments_scalar(const Lanes& L, float* mean, float* m2, int64_t row, float e, float rc, bool first) {
+  if (!L.active || L.h != 0) return;
+  float mu = 0.0f, s2 = 0.0f;
+  if (!first) {
+    mu = mean[row];
+    s2 = m2[row];
+  }
+  const float d = e - mu;
+  mu = mu + d * rc;
+  s2 = s2 + d * (e - mu);
+  mean[row] = mu;
+  m2[row] = s2;
 }
 
 // sum q^2 over the whole chain (both K-halves; the padding registers are zero)

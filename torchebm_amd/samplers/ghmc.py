@@ -79,6 +79,10 @@ class GeneralizedHMC(BaseSampler):
     """
 
     fused_mlp = False
+    #: second opt-in, read by ``sample_moments`` only: with ``fused_mlp`` set too, an eligible ``MLPEnergy`` call of
+    #: ``sample_moments`` is ONE launch of ``ebm_kinetic_moments_mlp_f32`` (docs/design/kinetic_moments_mlp.md).  Off by default: with
+    #: ``fused_mlp`` alone ``sample_moments`` keeps the step-by-step recurrence and autograd's energies.
+    fused_mlp_moments = False
 
     def __init__(
         self,
@@ -206,7 +210,9 @@ class GeneralizedHMC(BaseSampler):
         carry ``rhat``, ``ess``, ``mean``, ``var`` and ``acceptance_rate`` (``[n_steps]``).  When ``n_steps - burn_in`` is
         odd one more transition is burnt.  On the fused route (see the module docstring) the call is ONE launch of
         ``ebm_kinetic_moments_f32`` and ``x_final``, ``v_final`` are ``sample(return_velocity=True)``'s for the same
-        generator state.  The caller's ``x`` and ``velocity`` are never written.
+        generator state.  On an eligible ``MLPEnergy`` with both opt-ins, ``fused_mlp`` and ``fused_mlp_moments``, it is ONE
+        launch of ``ebm_kinetic_moments_mlp_f32`` and matches ``sample()`` under ``fused_mlp`` in the same way (``friction =
+        inf``: plain HMC); with ``fused_mlp`` alone it stays step by step.  The caller's ``x`` and ``velocity`` are never written.
 
         Raises:
             ValueError: fewer than 4 counted steps, ``burn_in`` outside ``0 .. n_steps``, a ``velocity`` of another shape.

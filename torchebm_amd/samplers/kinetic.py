@@ -66,6 +66,10 @@ class UnderdampedLangevin(BaseSampler):
     #: ONE launch of ``ebm_kinetic_mlp_chain_f32`` instead of the eager route.  Off by default: the fused evaluation is
     #: three-way-split bf16 arithmetic at fp32 accuracy, not autograd's rounding, and the draws are the Philox field's, not torch's.
     fused_mlp = False
+    #: second opt-in, read by ``sample_moments`` only: with ``fused_mlp`` set too, an eligible ``MLPEnergy`` call of
+    #: ``sample_moments`` is ONE launch of ``ebm_kinetic_moments_mlp_f32`` (docs/design/kinetic_moments_mlp.md).  Off by default: with
+    #: ``fused_mlp`` alone ``sample_moments`` keeps the step-by-step recurrence and autograd's energies.
+    fused_mlp_moments = False
 
     def __init__(
         self,
@@ -189,8 +193,10 @@ class UnderdampedLangevin(BaseSampler):
         carry ``rhat``, ``ess``, ``mean``, ``var`` and ``kinetic_temperature``, the time- and chain-averaged ``v^2`` per
         coordinate: an estimate of ``T (1 - h^2 E'' / 4)``.  When ``n_steps - burn_in`` is odd one more step is burnt.  On
         the fused route (see the module docstring) the call is ONE launch of ``ebm_kinetic_moments_f32`` and ``x_final``,
-        ``v_final`` are ``sample(return_velocity=True)``'s for the same generator state.  The caller's ``x`` and
-        ``velocity`` are never written.
+        ``v_final`` are ``sample(return_velocity=True)``'s for the same generator state.  On an eligible ``MLPEnergy`` with
+        both opt-ins, ``fused_mlp`` and ``fused_mlp_moments``, it is ONE launch of ``ebm_kinetic_moments_mlp_f32`` and matches
+        ``sample()`` under ``fused_mlp`` in the same way; with ``fused_mlp`` alone it stays step by step.  The caller's ``x``
+        and ``velocity`` are never written.
 
         Raises:
             ValueError: fewer than 4 counted steps, ``burn_in`` outside ``0 .. n_steps``, a ``velocity`` of another shape.

@@ -7,13 +7,19 @@ pooled moments -- plus, under BAOAB, the running mean of ``v^2`` per coordinate 
 ``kinetic_temperature``): on a quadratic energy ``E'' = k`` its expectation is ``T (1 - h^2 k / 4)``, the step-size error read
 off the run.  Generalized HMC keeps none: its velocity law is exact and carries no information.
 
-Two execution routes, chosen once per call:
+Three execution routes, chosen once per call:
 
 ``fused``  what the sampler's own ``_route`` calls fused, with ``dim >= 1``: ONE launch of ``ebm_kinetic_moments_f32``
            (include/ebm_hip.h states the algorithm exactly; docs/design/kinetic_moments.md the kernels).  ``_rng.reserve``
            takes ``k + 1`` Philox steps for BAOAB and ``2 k + 1`` for GHMC, the coordinates ``sample()`` draws at: the final
            ``x`` and ``v`` are ``sample(return_velocity=True)``'s bit for bit.  GHMC's ``acceptance_rate`` is summed from the
            entry's accept mask while that stays under ``MASK_MAX_BYTES``, from its per-transition counters beyond.
+``fused_mlp``  what the sampler's ``_route`` calls ``fused_mlp`` (an eligible ``MLPEnergy`` under the opt-in ``fused_mlp``) AND the
+           sampler's second opt-in ``fused_mlp_moments = True``: ONE launch of ``ebm_kinetic_moments_mlp_f32``
+           (docs/design/kinetic_moments_mlp.md) -- the walk ``sample()`` runs under ``fused_mlp``, split-bf16 evaluation and
+           Philox draws, with the same reservation, so the final ``x`` and ``v`` are that ``sample(return_velocity=True)``'s
+           bit for bit; the energies are the kernel's, not autograd's; the acceptance as above.  With ``fused_mlp`` alone
+           the call stays on ``eager`` and returns what it always did.
 ``eager``  anything else, CPU included: the sampler's own ``sample(n_steps=1, velocity=v, return_velocity=True)`` per
            transition around :class:`RunningMoments`, with the same reciprocal table; the ``v^2`` mean by the same recurrence
            in the state's dtype.
@@ -44,6 +50,9 @@ def sample_moments(sampler, ghmc: bool, x, dim, n_steps, n_samples, burn_in, ene
     route, spec = sampler._route(x, None)
     if route == "fused" and x.shape[0] > 0 and x.shape[1] >= 1:
         state, v, res = _fused(sampler, ghmc, spec, x, velocity, int(n_steps), burn_in, h, bool(energy), generator)
+    elif route == "fused_mlp" and sampler.fused_mlp_moments and x.shape[0] > 0:
+        state, v, res = _fused(sampler, ghmc, spec, x, velocity, int(n_steps), burn_in, h, bool(energy), generator,
+                               entry="ebm_kinetic_moments_mlp_f32")
     else:
         state, v, res = _eager(sampler, ghmc, x, velocity, int(n_steps), burn_in, h, bool(energy), generator)
     return (state, res, v) if return_velocity else (state, res)
@@ -72,7 +81,7 @@ def _eager(sampler, ghmc, x, v, k, burn_in, h, energy, generator):
     return x, v, res
 
 
-def _fused(sampler, ghmc, spec, x, v, k, burn_in, h, energy, generator):
+def _fused(sampler, ghmc, spec, x, v, k, burn_in, h, energy, generator, entry: str = "ebm_kinetic_moments_f32"):
     n, dim = x.shape
     dev = x.device
     state = _lib.dense_f32(x).clone()  # the kernel updates in place; never the caller's tensors
@@ -92,7 +101,7 @@ def _fused(sampler, ghmc, spec, x, v, k, burn_in, h, energy, generator):
         counts = torch.zeros(k, dtype=torch.int32, device=dev)  # (uint32 counters in an int32 tensor)
     seed, step0 = _rng.reserve(generator, dev, (2 * k if ghmc else k) + 1)
     _lib.call(
-        "ebm_kinetic_moments_f32",
+        entry,
         spec.to_c(), _lib.ptr(state), _lib.ptr(vel), n, dim, SAMPLER_GHMC if ghmc else SAMPLER_BAOAB, k, burn_in,
         int(sampler.n_leapfrog_steps) if ghmc else 0, float(sampler.get_scheduled_value("step_size")), sampler.friction,
         sampler.temperature, int(draw_v0), _lib.ptr(recip), _lib.ptr(mom), _lib.ptr(e_mom), _lib.ptr(v2), None, None, None,
