@@ -574,6 +574,54 @@ EBM_API int ebm_chain_moments_f32(const ebm_energy_t* energy, float* x, int64_t 
                                   const float* u, uint64_t seed, uint64_t offset, void* stream);
 
 /*
+ * Per-chain running moments of Langevin dynamics on the MLP energy: the statistics of ebm_chain_moments_f32 above -- the same
+ * parameter list, the same counted states, recip table, Welford recurrence and layouts of mom, e_mom, traj and e_traj -- around
+ * the Euler-Maruyama walk on the matrix-core evaluation of the MLP, in ONE launch (an addition to ABI 9: nothing else moved;
+ * ebm_chain_moments_f32 still refuses the MLP).  One wave walks 32 chains.  sampler must be 0; n_leapfrog, eps, accept_mask,
+ * accept_count and u are ignored (HMC on the MLP with running moments: ebm_kinetic_moments_mlp_f32, generalized HMC at infinite
+ * friction).
+ *
+ * Transition (eta, sqrt_eta, noise_coef: constants): ebm_langevin_chain_f32's update without clamp,
+ *     x1 = x - eta * dE/dx;   dw = z * sqrt_eta;   x' = x1 + noise_coef * dw
+ * every operation rounded on its own.  The gradient is raw: a NaN stays in its chain.  z is the normal field at Philox step
+ * offset + s, element chain * dim + col -- the coordinates ebm_langevin_chain_f32 draws at -- or the injected
+ * noise[k_steps, n_chains, dim].  A call owns the steps offset .. offset + k_steps - 1.  The gradient comes from the general
+ * evaluation of the MLP walks, not from the specialised Langevin chain kernels: the final x is ebm_langevin_chain_f32's draw for
+ * draw and operation for operation in the update, but not guaranteed bit for bit.
+ *
+ * Counted states.  The first burn_in steps are not counted; k_steps - burn_in == 2 h with h >= 2; a counted state is the state
+ * AFTER the step.  Per coordinate, per half and with c = 1 .. h
+ *     d = x - mean;   mean = mean + d * recip[c - 1];   M2 = M2 + d * (x - mean)
+ * in fp32, every operation rounded on its own; mom is float[4][n_chains][dim] (mean_a, M2_a, mean_b, M2_b), e_mom NULL or
+ * float[4][n_chains].  traj: NULL, or float[n_chains][2 h][dim], the counted states; e_traj: NULL, or float[n_chains][2 h],
+ * their energies (written with or without e_mom).
+ *
+ * Energies add at most one evaluation.  Evaluation i >= 1 is made at the state behind step i - 1, the counted state.  With
+ * e_mom or e_traj given the launch makes k_steps + 1 evaluations; with both NULL exactly k_steps: nothing is evaluated behind
+ * the last step.  The value counted is the unclamped one.
+ *
+ * Working storage.  The pairs do not live in registers: mom and e_mom are WORKING STORAGE during the launch -- each counted step
+ * reads a chain's pair from them and writes it back (a lane reads only what it stored itself) -- and defined at return.  At
+ * c == 1 the pair starts from zero and the planes are not read: the caller need not initialise them, and whatever they held (a
+ * NaN included) never reaches the output.  They must not overlap each other or any other buffer of the call.  Columns past
+ * dim and rows past n_chains never reach memory; 64-bit row indices.
+ *
+ * The evaluation is three-way split bf16 (or exact-f32 MFMA) arithmetic with fp32 accumulation: fp32 accuracy, not autograd's
+ * rounding.
+ *
+ * Refusals, all in front of any device access and of the early return for n_chains == 0.  EBM_EINVAL: a NULL energy, x, mom or
+ * recip; n_chains < 0; sampler != 0; burn_in < 0 or k_steps - burn_in not 2 h with h >= 2; eta, sqrt_eta or noise_coef NaN or
+ * infinite.  EBM_EKIND: a kind other than EBM_ENERGY_MLP.  EBM_EDIM: a hidden width (energy->n_comp) other than 64 / 128 or
+ * dim outside 1 .. 128 (the message names both).  x, mom, traj and noise must be 16-byte aligned.  No H = 256, no pre-split W1
+ * image (energy->aux is ignored), no tables, no clamp, no Heun.
+ */
+EBM_API int ebm_chain_moments_mlp_f32(const ebm_energy_t* energy, float* x, int64_t n_chains, int32_t dim, int32_t sampler,
+                                      int32_t k_steps, int32_t burn_in, float eta, float sqrt_eta, float noise_coef,
+                                      int32_t n_leapfrog, float eps, const float* recip, float* mom, float* e_mom, float* traj,
+                                      float* e_traj, uint8_t* accept_mask, uint32_t* accept_count, const float* noise_or_p,
+                                      const float* u, uint64_t seed, uint64_t offset, void* stream);
+
+/*
  * Underdamped (kinetic) Langevin dynamics in the BAOAB splitting (Leimkuhler & Matthews 2013): k_steps transitions of a walker
  * per chain that carries a velocity beside its position, in ONE launch (an addition to ABI 9: nothing else moved).  Unit mass,
  * friction gamma > 0, temperature T > 0 (the target is exp(-E / T)), step h > 0.  One gradient evaluation per step, as

@@ -46,6 +46,7 @@ EXPORTS = (
     "ebm_ais_chain_f32",
     "ebm_ais_mlp_chain_f32",
     "ebm_chain_moments_f32",
+    "ebm_chain_moments_mlp_f32",
     "ebm_kinetic_chain_f32",
     "ebm_kinetic_mlp_chain_f32",
     "ebm_ghmc_chain_f32",
@@ -161,6 +162,10 @@ _PROTOTYPES = {
         [_ENERGY_P, _p, _p, _i64, _i32, _i32, _i32, _p, _p, _f, _f, _p, _p, _p, _p, _p, _u64, _u64, _p],
     ),
     "ebm_chain_moments_f32": (
+        C.c_int,
+        [_ENERGY_P, _p, _i64, _i32, _i32, _i32, _i32, _f, _f, _f, _i32, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p, _u64, _u64, _p],
+    ),
+    "ebm_chain_moments_mlp_f32": (  # the same parameter list, the Langevin walker on the MLP energy
         C.c_int,
         [_ENERGY_P, _p, _i64, _i32, _i32, _i32, _i32, _f, _f, _f, _i32, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p, _u64, _u64, _p],
     ),

@@ -552,6 +552,37 @@ int ebm_chain_moments_f32(const ebm_energy_t* energy, float* x, int64_t n_chains
   return moments_chain_launch(q, (hipStream_t)stream);
 }
 
+int ebm_chain_moments_mlp_f32(const ebm_energy_t* energy, float* x, int64_t n_chains, int32_t dim, int32_t sampler, int32_t k_steps,
+                              int32_t burn_in, float eta, float sqrt_eta, float noise_coef, int32_t n_leapfrog, float eps,
+                              const float* recip, float* mom, float* e_mom, float* traj, float* e_traj, uint8_t* accept_mask,
+                              uint32_t* accept_count, const float* noise, const float* u, uint64_t seed, uint64_t offset,
+                              void* stream) {
+  const char* who = "ebm_chain_moments_mlp_f32";
+  (void)n_leapfrog; (void)eps; (void)accept_mask; (void)accept_count; (void)u;  // the HMC half of the shared parameter list
+  if (int r = check_energy(energy, dim, who)) return r;
+  if (energy->kind != EBM_ENERGY_MLP)
+    return fail(EBM_EKIND, "%s: this entry walks the MLP energy only (ebm_chain_moments_f32 takes the analytic kinds)", who);
+  // (the dim range is langevin_moments_mlp_check_shape's to refuse)
+  if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
+  if (n_chains < 0) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d]", who, (long long)n_chains, dim);
+  if (sampler != 0)
+    return fail(EBM_EINVAL, "%s: sampler=%d (0 = Langevin; for HMC on the MLP: ebm_kinetic_moments_mlp_f32, generalized HMC at infinite friction)",
+                who, sampler);
+  if (k_steps < 0 || burn_in < 0 || burn_in > k_steps || ((k_steps - burn_in) & 1) || (k_steps - burn_in) / 2 < 2)
+    return fail(EBM_EINVAL, "%s: k_steps=%d burn_in=%d (k_steps - burn_in must be 2 h with h >= 2)", who, k_steps, burn_in);
+  if (!std::isfinite(eta) || !std::isfinite(sqrt_eta) || !std::isfinite(noise_coef))
+    return fail(EBM_EINVAL, "%s: eta=%g sqrt_eta=%g noise_coef=%g (all must be finite)", who, (double)eta, (double)sqrt_eta,
+                (double)noise_coef);
+  if (!recip || !mom) return fail(EBM_EINVAL, "%s: recip / mom is NULL", who);
+  if (int r = langevin_moments_mlp_check_shape(energy->n_comp, dim)) return r;
+  if (n_chains == 0) return 0;
+  if (!aligned16(x) || !aligned16(mom) || (traj && !aligned16(traj)) || (noise && !aligned16(noise)))
+    return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  const LangevinMomentsChainReq q{*energy, x, n_chains, dim, k_steps, burn_in, eta, sqrt_eta, noise_coef, recip, mom, e_mom, traj,
+                                  e_traj, noise, seed, offset};
+  return langevin_moments_mlp_chain_launch(q, (hipStream_t)stream);
+}
+
 // The request of both underdamped-Langevin entries: the constants of the splitting, formed in double, each rounded once
 static KineticChainReq kinetic_request(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t k_steps,
                                        double h, double gamma, double temperature, int32_t draw_v0, int32_t thin, float* traj,

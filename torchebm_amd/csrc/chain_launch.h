@@ -142,6 +142,24 @@ struct MomentsChainReq {
   int32_t half_len() const { return (k_steps - burn_in) / 2; }
 };
 
+struct LangevinMomentsChainReq {
+  const ebm_energy_t& e;   // the MLP energy
+  float* x;                // [n_chains, dim], in/out
+  int64_t n_chains;
+  int32_t dim, k_steps, burn_in;
+  float eta, sqrt_eta, noise_coef;
+  const float* recip;      // device [half_len()]
+  float* mom;              // [4, n_chains, dim]
+  float* e_mom;            // [4, n_chains] or null
+  float* traj;             // [n_chains, 2 half_len(), dim] or null
+  float* e_traj;           // [n_chains, 2 half_len()] or null
+  const float* noise;      // [k_steps, n_chains, dim] or null
+  uint64_t seed, offset;
+
+  RngKey key() const { return RngKey{(uint32_t)seed, (uint32_t)(seed >> 32)}; }
+  int32_t half_len() const { return (k_steps - burn_in) / 2; }
+};
+
 struct KineticChainReq {
   const ebm_energy_t& e;
   float* x;                // [n_chains, dim], in/out
@@ -330,6 +348,9 @@ int ais_mlp_check_shape(int32_t hidden, int32_t dim);  // 0, or the refusal (hid
 // ---------------------------------------------------------------------------------
 int moments_chain_launch(const MomentsChainReq&, hipStream_t);
 int moments_check_geometry(int32_t dim);  // 0, or the refusal (dim > 256)
+// ... of the Langevin walker on the MLP energy (mlp_wide_langevin_moments.hip: 32 chains per wave around the matrix-core evaluation, k_steps of them per call and one more with energies, the Welford pairs kept in the caller's planes)
+int langevin_moments_mlp_chain_launch(const LangevinMomentsChainReq&, hipStream_t);
+int langevin_moments_mlp_check_shape(int32_t hidden, int32_t dim);  // 0, or the refusal (hidden width not 64 / 128, dim outside 1 .. 128)
 
 // ---------------------------------------------------------------------------------
 // Underdamped Langevin, BAOAB (kinetic.hip: a walker per chain with position, velocity and carried gradient in registers)

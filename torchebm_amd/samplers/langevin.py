@@ -190,7 +190,8 @@ class LangevinDynamics(BaseSampler):
         (``ValueError``).  Schedulers are reset first, as in ``sample()``.  On the fused route (CUDA fp32, an analytic
         energy, ``dim <= 256``, constant step size and noise scale, no clamp) the call is ONE launch of
         ``ebm_chain_moments_f32`` and, for the element-wise energies, ``x_final`` is ``sample()``'s for the same generator
-        state bit for bit; anything else runs ``sample(n_steps=1)`` per step around the same recurrence."""
+        state bit for bit; with the opt-in ``fused_mlp_moments`` an eligible ``MLPEnergy`` call is ONE launch of
+        ``ebm_chain_moments_mlp_f32``; anything else runs ``sample(n_steps=1)`` per step around the same recurrence."""
         from .moments import sample_moments
 
         return sample_moments(self, False, x, dim, n_steps, n_samples, burn_in, energy, generator)
@@ -371,6 +372,14 @@ class LangevinDynamics(BaseSampler):
     #: step, 12 % more chain-steps per second on BASELINE config 2 (``EBM_CHAIN_CONTRACTED``, include/ebm_hip.h; bench.py
     #: ``config2_fused_arithmetic``).  Calls without such a kernel run the default arithmetic.
     fused_arithmetic: bool = False
+
+    #: Opt-in, read by ``sample_moments`` only: an ``MLPEnergy`` call that ``sample()`` runs fused (hidden 64 / 128,
+    #: ``dim == in_dim <= 128``, CUDA fp32, constant step size and noise scale, no clamp, plain Euler-Maruyama, no autocast) is ONE
+    #: launch of ``ebm_chain_moments_mlp_f32`` (docs/design/langevin_moments_mlp.md) instead of ``n_steps`` calls of
+    #: ``sample(n_steps=1)``.  Off by default: the energies become the kernel's split-bf16 / exact-f32 values, not autograd's, and
+    #: the gradient comes from the general walk evaluation, not from the Langevin chain kernels ``sample()`` runs on the MLP --
+    #: ``x_final`` is ``sample()``'s draw for draw and operation for operation in the update, but not guaranteed bit for bit.
+    fused_mlp_moments = False
 
     #: Opt-in: let the fused route update the caller's ``x`` in place and return it.  Off by default: the reference never
     #: mutates its input.  For the plain Euler-Maruyama call this saves the allocation of the returned state (256 MiB at

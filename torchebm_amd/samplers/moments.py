@@ -7,13 +7,19 @@ halves of the remaining ``2 h`` states -- a Welford pair per half, fp32, beside 
 moments.  No trajectory is written: the statistics are taken where the state is (``include/ebm_hip.h``,
 ``ebm_chain_moments_f32``, states the algorithm exactly; docs/design/moments.md).
 
-Two execution routes, chosen once per call (:func:`fused_moments_eligible`):
+Three execution routes, chosen once per call (:func:`fused_moments_eligible`):
 
 ``fused``  CUDA fp32, an analytic energy with a fused spec (not the MLP), a 2-D state with ``dim <= 256``, constant schedulers,
            no clamp, no ``model_kwargs``, and for HMC ``mass is None`` with the plain leapfrog integrator: ONE launch of
            ``ebm_chain_moments_f32``; ``_rng.reserve`` of ``k`` Philox steps for Langevin and ``2 k`` for HMC -- the
            coordinates ``sample()`` draws at, so for the element-wise energies under Langevin the final states are
            ``sample()``'s bit for bit.
+``fused_mlp``  Langevin on an ``MLPEnergy`` under the sampler's opt-in ``fused_mlp_moments = True``
+           (:func:`fused_mlp_moments_eligible`: what ``sample()`` runs fused, hidden width 64 / 128, ``dim == in_dim <= 128``,
+           constant schedulers, no clamp, plain Euler-Maruyama, no autocast): ONE launch of ``ebm_chain_moments_mlp_f32``
+           (docs/design/langevin_moments_mlp.md) with the reservation of ``sample(n_steps=k)``; the energies are the kernel's,
+           not autograd's, and ``x_final`` is ``sample()``'s draw for draw, not guaranteed bit for bit.  Without the opt-in the
+           call stays on ``eager`` and returns what it always did.
 ``eager``  anything else, CPU included: the sampler's own route, one ``sample(n_steps=1)`` per transition, around the same
            Welford recurrence with the same reciprocal table (:class:`RunningMoments`).
 
@@ -212,6 +218,34 @@ def fused_moments_eligible(*, is_cuda: bool, dtype: torch.dtype, ndim: int, dim:
                 and extras_ok)
 
 
+def fused_mlp_moments_eligible(*, opted_in: bool, dtype: torch.dtype, ndim: int, n: int, dim: int, route: Optional[str],
+                               spec_kind: Optional[int], hidden: Optional[int], in_dim: Optional[int], constant: bool,
+                               plain_integrator: bool, autocast: bool, has_clamp: bool) -> bool:
+    """The routing predicate of ``LangevinDynamics.sample_moments`` to ``ebm_chain_moments_mlp_f32``.  ``opted_in``: the sampler's
+    ``fused_mlp_moments``; ``route``, ``spec_kind``, ``hidden``: what ``sampler._route(x, {})`` returned -- the route's name
+    (``"fused"`` only for a CUDA fp32 state: the sampler decides that, here as for ``sample()``), the spec's kind and its
+    ``n_comp`` (``None`` without a spec); ``in_dim``: the model's."""
+    return bool(opted_in and dtype == torch.float32 and ndim == 2 and n > 0 and route == "fused"
+                and spec_kind == _lib.ENERGY_MLP and hidden in (64, 128) and 1 <= dim <= 128 and dim == in_dim and constant
+                and plain_integrator and not autocast and not has_clamp)
+
+
+def _route_mlp(sampler, x: torch.Tensor):
+    """The fused spec of an eligible ``LangevinDynamics`` call on an ``MLPEnergy`` under ``fused_mlp_moments``, or ``None``."""
+    from ..integrators.em import EulerMaruyamaIntegrator
+
+    if not getattr(sampler, "fused_mlp_moments", False) or x.ndim != 2:
+        return None
+    route, spec = sampler._route(x, {})
+    ok = fused_mlp_moments_eligible(
+        opted_in=True, dtype=x.dtype, ndim=x.ndim, n=x.shape[0], dim=x.shape[1], route=route,
+        spec_kind=None if spec is None else spec.kind, hidden=None if spec is None else spec.n_comp,
+        in_dim=getattr(sampler.model, "in_dim", None), constant=all(s.is_constant() for s in sampler.schedulers.values()),
+        plain_integrator=type(sampler.integrator) is EulerMaruyamaIntegrator,
+        autocast=bool(sampler.use_mixed_precision and sampler.autocast_available), has_clamp=sampler.clamp is not None)
+    return spec if ok else None
+
+
 def _route(sampler, hmc: bool, x: torch.Tensor):
     from ..integrators.em import EulerMaruyamaIntegrator
     from ..integrators.symplectic import LeapfrogIntegrator
@@ -247,6 +281,9 @@ def sample_moments(sampler, hmc: bool, x, dim, n_steps, n_samples, burn_in, ener
     spec = _route(sampler, hmc, x) if x.shape[0] > 0 else None
     if spec is not None:
         return _fused(sampler, hmc, spec, x, int(n_steps), burn_in, h, bool(energy), generator)
+    spec = None if hmc else _route_mlp(sampler, x)
+    if spec is not None:
+        return _fused(sampler, False, spec, x, int(n_steps), burn_in, h, bool(energy), generator, entry="ebm_chain_moments_mlp_f32")
     return _eager(sampler, hmc, x, int(n_steps), burn_in, h, bool(energy), generator)
 
 
@@ -266,7 +303,7 @@ def _eager(sampler, hmc, x, k, burn_in, h, energy, generator):
     return x, acc.result(rate)
 
 
-def _fused(sampler, hmc, spec, x, k, burn_in, h, energy, generator):
+def _fused(sampler, hmc, spec, x, k, burn_in, h, energy, generator, entry: str = "ebm_chain_moments_f32"):
     from .langevin import em_coefficients
 
     n, dim = x.shape
@@ -289,7 +326,7 @@ def _fused(sampler, hmc, spec, x, k, burn_in, h, energy, generator):
     else:
         seed, step0 = _rng.reserve(generator, dev, k)
         a, sq, coef = em_coefficients(sampler.schedulers["step_size"].get_value(), sampler.schedulers["noise_scale"].get_value())
-        _lib.call("ebm_chain_moments_f32", spec.to_c(), _lib.ptr(state), n, dim, SAMPLER_LANGEVIN, k, burn_in, a, sq, coef,
+        _lib.call(entry, spec.to_c(), _lib.ptr(state), n, dim, SAMPLER_LANGEVIN, k, burn_in, a, sq, coef,
                   0, 0.0, _lib.ptr(recip), _lib.ptr(mom), _lib.ptr(e_mom), None, None, None, None, None, None, seed, step0,
                   stream)
         rate = None
