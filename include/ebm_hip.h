@@ -448,6 +448,54 @@ EBM_API int ebm_tempering_hmc_mlp_chain_f32(const ebm_energy_t* energy, float* x
                                             const float* u_accept, const float* u_swap, uint64_t seed, uint64_t step0, void* stream);
 
 /*
+ * Replica-exchange Langevin on the MLP energy: the algorithm, the parameter list, the slot matrix (row c * R + r, slot 0 the
+ * target), the Philox coordinates, the outputs and the counters of ebm_tempering_chain_f32 for EBM_ENERGY_MLP -- k_steps
+ * Euler-Maruyama steps of every slot and the swap events between them in ONE launch around the matrix-core evaluation (an addition
+ * to ABI 9: nothing else moved; ebm_tempering_chain_f32 keeps refusing the MLP).  docs/design/tempering_mlp.md.
+ *
+ * Step s (0 .. k_steps - 1), every slot r of every ladder c:
+ *     E, g = the evaluation at x            raw: no clamp on either, a NaN stays in its row
+ *     x1 = x - eta * g;  dw = z * sqrt_eta;  x = x1 + noise_coef[r] * dw     every operation rounded on its own
+ *                                           z: the normal field at step step0 + 2 s, element (c * R + r) * dim + col
+ * Columns past dim are held at 0.
+ *
+ * Swap event m = (s + 1) / swap_every - 1 after step s when (s + 1) % swap_every == 0: even events pair (0,1), (2,3), .., odd
+ * events (1,2), (3,4), ..; delta = (beta[r] - beta[r + 1]) * (E_r - E_{r+1}) on the raw fp32 energies of the states behind step
+ * s; the pair swaps iff delta == delta and u < exp(min(delta, 0)), u the uniform field at step step0 + 2 s + 1, element
+ * c * R + r, the lower slot's row.  A swap exchanges the two STATES (rows c * R + r and c * R + r + 1 of x).  The energies of an
+ * event are those of the evaluation that yields step s + 1's gradient, made at the state behind step s; the gradient moves with
+ * the state, so an event costs no evaluation: a call makes k_steps + 1 evaluations when k_steps % swap_every == 0 (the last one
+ * for the last event's energies alone) and k_steps otherwise.  A kept step behind the last step with no event due there
+ * evaluates nothing: the state behind step k_steps - 1 is stored as it stands.
+ *
+ * Outputs and draws: after step s and its event, when (s + 1) % thin == 0, slot 0's state goes to traj[c, (s + 1) / thin - 1]
+ * (traj: [n_ladders, k_steps / thin, dim] or NULL); swap_counts: NULL or device uint32[2 (R - 1)] (attempts of pair (p, p + 1) at
+ * p, accepts at R - 1 + p), ADDED to, once per workgroup at the end of the call; noise[k_steps, n_ladders * R, dim] /
+ * u[k_steps / swap_every, n_ladders * R]: both NULL (native draws) or both given (only the lower-slot entries of u are read;
+ * with no event in the call u is not read).  The call owns the Philox steps step0 .. step0 + 2 k_steps - 1.
+ * x is read once and written once, at the end of the call; columns past dim and rows past n_ladders * R never reach memory;
+ * 64-bit row indices.
+ *
+ * Two calls equal one whenever the first holds an even number of events (m restarts at 0 in every call): (n1, step0) then
+ * (n2, step0 + 2 n1) with n1 % (2 swap_every) == 0 gives the bits of one call of n1 + n2 -- the first call's last evaluation and
+ * the second call's first are the same function of the same rows.  With no event in the call, slot r's rows are
+ * ebm_chain_moments_mlp_f32 chains at noise_coef[r] on the same draws, bit for bit.
+ *
+ * The evaluation is three-way split bf16 (or exact-f32 MFMA) arithmetic with fp32 accumulation: fp32 accuracy, not autograd's
+ * rounding.
+ *
+ * Refusals, all in front of any device access and of the early return for n_ladders == 0: a NULL energy, x, noise_coef or beta;
+ * k_steps, thin or swap_every below 1; n_ladders < 0; draws given in part; eta or sqrt_eta NaN or infinite; x, traj or noise not
+ * 16-byte aligned (EBM_EINVAL); a kind other than EBM_ENERGY_MLP (EBM_EKIND); a hidden width (energy->n_comp) other than
+ * 64 / 128, dim outside 1 .. 128 or n_replicas not in {2, 4, 8, 16, 32} (EBM_EDIM, the message names the three numbers).  No
+ * H = 256, no pre-split W1 image (energy->aux is ignored), no tables, no clamp, no diagnostics records.
+ */
+EBM_API int ebm_tempering_mlp_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_ladders, int32_t n_replicas, int32_t dim,
+                                        int32_t k_steps, float eta, float sqrt_eta, const float* noise_coef, const float* beta,
+                                        int32_t swap_every, int32_t thin, float* traj, uint32_t* swap_counts, const float* noise,
+                                        const float* u, uint64_t seed, uint64_t step0, void* stream);
+
+/*
  * Annealed importance sampling (Neal 2001): every chain walks ONE state from the base N(0, sigma0^2 I) to the target through
  * n_temps tempered laws and accumulates the importance weight whose mean estimates Z / Z_0 -- the whole walk in ONE launch (an
  * addition to ABI 9: nothing else moved).  The third member of the tempered family: the replica-exchange entries run R

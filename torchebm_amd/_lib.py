@@ -41,6 +41,7 @@ EXPORTS = (
     "ebm_hmc_chain_f32",
     "ebm_hmc_chain_audit_f32",
     "ebm_tempering_chain_f32",
+    "ebm_tempering_mlp_chain_f32",
     "ebm_tempering_hmc_chain_f32",
     "ebm_tempering_hmc_mlp_chain_f32",
     "ebm_ais_chain_f32",
@@ -142,6 +143,10 @@ _PROTOTYPES = {
         [_ENERGY_P, _p, _i64, _i32, _i32, _i32, _f, _p, _i32, _d, _p, _i32, _p, _p, _p, _p, _p, _u64, _u64, _p],
     ),
     "ebm_tempering_chain_f32": (
+        C.c_int,
+        [_ENERGY_P, _p, _i64, _i32, _i32, _i32, _f, _f, _p, _p, _i32, _i32, _p, _p, _p, _p, _u64, _u64, _p],
+    ),
+    "ebm_tempering_mlp_chain_f32": (  # the same parameter list, on the MLP energy
         C.c_int,
         [_ENERGY_P, _p, _i64, _i32, _i32, _i32, _f, _f, _p, _p, _i32, _i32, _p, _p, _p, _p, _u64, _u64, _p],
     ),

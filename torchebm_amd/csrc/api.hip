@@ -432,6 +432,32 @@ int ebm_tempering_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_ladd
   return tempering_chain_launch(q, (hipStream_t)stream);
 }
 
+int ebm_tempering_mlp_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_ladders, int32_t n_replicas, int32_t dim,
+                                int32_t k_steps, float eta, float sqrt_eta, const float* noise_coef, const float* beta,
+                                int32_t swap_every, int32_t thin, float* traj, uint32_t* swap_counts, const float* noise,
+                                const float* u, uint64_t seed, uint64_t step0, void* stream) {
+  const char* who = "ebm_tempering_mlp_chain_f32";
+  if (int r = check_energy(energy, dim, who)) return r;
+  if (energy->kind != EBM_ENERGY_MLP)
+    return fail(EBM_EKIND, "%s: this entry walks the MLP energy only (ebm_tempering_chain_f32 takes the analytic kinds)", who);
+  // (the dim range and the ladder lengths are tempering_mlp_check_shape's to refuse)
+  if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
+  if (!noise_coef || !beta) return fail(EBM_EINVAL, "%s: noise_coef / beta is NULL", who);
+  if (n_ladders < 0) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d, %d]", who, (long long)n_ladders, n_replicas, dim);
+  if (k_steps < 1 || swap_every < 1 || thin < 1)
+    return fail(EBM_EINVAL, "%s: k_steps=%d swap_every=%d thin=%d (all must be >= 1)", who, k_steps, swap_every, thin);
+  if ((noise == nullptr) != (u == nullptr)) return fail(EBM_EINVAL, "%s: noise and u must be given together", who);
+  if (!std::isfinite(eta) || !std::isfinite(sqrt_eta))
+    return fail(EBM_EINVAL, "%s: eta=%g sqrt_eta=%g (both must be finite)", who, (double)eta, (double)sqrt_eta);
+  if (!aligned16(x) || (traj && !aligned16(traj)) || (noise && !aligned16(noise)))
+    return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  if (int r = tempering_mlp_check_shape(energy->n_comp, dim, n_replicas)) return r;
+  if (n_ladders == 0) return 0;
+  const TemperingChainReq q{*energy, x, n_ladders, n_replicas, dim, k_steps, eta, sqrt_eta, noise_coef, beta, swap_every, thin,
+                            traj, swap_counts, noise, u, seed, step0};
+  return tempering_mlp_chain_launch(q, (hipStream_t)stream);
+}
+
 int ebm_tempering_hmc_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_ladders, int32_t n_replicas, int32_t dim,
                                 int32_t n_mh, int32_t n_leapfrog, const float* eps, const float* sqrt_temp, const float* beta,
                                 int32_t swap_every, int32_t thin, float* traj, uint8_t* accept_mask, uint32_t* accept_counts,

@@ -322,6 +322,10 @@ bool matrix_hmc_diag_plan(const ebm_energy_t&, int64_t n_chains, int32_t dim, di
 // ---------------------------------------------------------------------------------
 int tempering_chain_launch(const TemperingChainReq&, hipStream_t);
 int tempering_check_geometry(int32_t n_replicas, int32_t dim);  // 0, or the refusal (dim > 1024, ladder wider than a workgroup)
+// ... on the MLP energy (mlp_wide_tempering_langevin.hip: the same request; 32 slot rows per wave around the matrix-core evaluation, one per step, a swap moves state and gradient between neighbouring lanes)
+int tempering_mlp_chain_launch(const TemperingChainReq&, hipStream_t);
+// 0, or the refusal (hidden width not 64 / 128, dim outside 1 .. 128, n_replicas not in {2, 4, 8, 16, 32})
+int tempering_mlp_check_shape(int32_t hidden, int32_t dim, int32_t n_replicas);
 
 // ---------------------------------------------------------------------------------
 // Replica-exchange HMC (tempering_hmc.hip: the same ladders, a Metropolis-corrected HMC transition in every slot)

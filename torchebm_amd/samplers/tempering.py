@@ -10,14 +10,18 @@ propose to exchange their states, accepted with probability ``min(1, exp((beta_r
 ``beta_r = 1 / (sigma^2 T_r)``.  Even events pair the slots (0,1), (2,3), ..., odd events (1,2), (3,4), ....  The hot
 slots cross barriers that the target slot does not, and the swaps carry those crossings down the ladder.
 
-Two execution routes, chosen once per ``sample()`` call (``_route``):
+The execution routes, chosen once per ``sample()`` call (``_route``):
 
 ``fused``  CUDA fp32 state, one of the analytic energies (not the MLP), float step size and noise scale, and a ladder
            that fits one workgroup (``R * G <= 256``, ``G`` the lanes per row): the whole call -- steps, swap events,
            Philox draws, thinned trajectory of slot 0, swap counters -- is ONE launch of ``ebm_tempering_chain_f32``
            (include/ebm_hip.h states the algorithm exactly; docs/design/tempering.md the kernel).
-``eager``  everything else (CPU, any other ``BaseModel`` such as ``MLPEnergy`` or a hand-written energy, schedulers): the
-           same algorithm in torch ops, drawing ``randn(n, R, dim)`` per step and ``rand(n, R)`` per event.
+``fused_mlp``  only with the opt-in ``sampler.fused_mlp_ladder = True``: an ``MLPEnergy`` of hidden width 64 / 128 with
+           ``dim == in_dim <= 128`` and a ladder of 2, 4, 8, 16 or 32 slots, constant step size and noise scale: ONE
+           launch of ``ebm_tempering_mlp_chain_f32`` with the same parameter list and Philox coordinates
+           (docs/design/tempering_mlp.md).
+``eager``  everything else (CPU, any other ``BaseModel`` such as ``MLPEnergy`` without the opt-in or a hand-written energy,
+           schedulers): the same algorithm in torch ops, drawing ``randn(n, R, dim)`` per step and ``rand(n, R)`` per event.
 
 A fused-eligible call never falls back to eager: a missing library or a failing launch raises.
 
@@ -102,7 +106,15 @@ class ReplicaExchangeLangevin(_LadderSampler):
         temperatures: strictly increasing, positive, at least two; the first is the target's.
         swap_every: a swap event follows every ``swap_every``-th step.
         dtype, device: where the ladders live.
+
+    ``fused_mlp_ladder`` (class attribute, ``False``): set it on a sampler to send an eligible ``MLPEnergy`` call -- hidden
+    width 64 / 128, ``dim == in_dim <= 128``, ``R`` in {2, 4, 8, 16, 32}, constant step size and noise scale -- to the route
+    ``fused_mlp``: ONE launch of ``ebm_tempering_mlp_chain_f32`` per call, the matrix-core evaluation inside the walk (split-bf16
+    / exact-f32 MFMA arithmetic at fp32 accuracy, not autograd's rounding) and Philox draws instead of torch's generator,
+    never a fallback.  Off by default: a default sampler on an MLP keeps its eager bits.
     """
+
+    fused_mlp_ladder = False
 
     def __init__(
         self,
@@ -132,7 +144,13 @@ class ReplicaExchangeLangevin(_LadderSampler):
             return "eager", None
         rows = x.view(-1, x.shape[-1])
         spec = fused_spec_for(self.model, rows, None)
-        if spec is None or spec.kind == _lib.ENERGY_MLP:
+        if spec is not None and spec.kind == _lib.ENERGY_MLP:
+            dim = rows.shape[1]
+            if (self.fused_mlp_ladder and self.n_replicas in FUSED_MLP_LADDERS and spec.n_comp in (64, 128)
+                    and dim == getattr(self.model, "in_dim", None) and dim <= FUSED_MLP_MAX_DIM):
+                return "fused_mlp", spec
+            return "eager", None
+        if spec is None:
             return "eager", None
         if self.n_replicas > 64 or self.n_replicas * lanes_per_row(rows.shape[1]) > 256:
             return "eager", None
@@ -173,6 +191,9 @@ class ReplicaExchangeLangevin(_LadderSampler):
         route, spec = self._route(x)
         if route == "fused":
             state, traj, diag = self._sample_fused(x, spec, n_steps, thin, return_trajectory, return_diagnostics, generator)
+        elif route == "fused_mlp":
+            state, traj, diag = self._sample_fused(x, spec, n_steps, thin, return_trajectory, return_diagnostics, generator,
+                                                   entry="ebm_tempering_mlp_chain_f32")
         else:
             state, traj, diag = self._sample_eager(x, n_steps, thin, return_trajectory, return_diagnostics, generator)
         out = traj if return_trajectory else (state if return_replicas else state[:, 0].contiguous())
@@ -220,7 +241,7 @@ class ReplicaExchangeLangevin(_LadderSampler):
         return x, traj, diag
 
     # ---------------------------------------------------------------------------------
-    # route: one launch of ebm_tempering_chain_f32
+    # routes: one launch of ebm_tempering_chain_f32, or (fused_mlp) of ebm_tempering_mlp_chain_f32 -- the same parameter list
     # ---------------------------------------------------------------------------------
     def _ladder_on(self, device: torch.device, sigma: float) -> Tuple[torch.Tensor, torch.Tensor]:
         """The two device arrays of the ladder, kept for the next call with the same noise scale."""
@@ -232,7 +253,8 @@ class ReplicaExchangeLangevin(_LadderSampler):
             self._ladder_cache = cached
         return cached[1], cached[2]
 
-    def _sample_fused(self, x, spec: FusedSpec, n_steps, thin, want_traj, want_diag, generator):
+    def _sample_fused(self, x, spec: FusedSpec, n_steps, thin, want_traj, want_diag, generator,
+                      entry: str = "ebm_tempering_chain_f32"):
         n, R, dim = x.shape
         n_kept = n_steps // thin
         state = _lib.dense_f32(x).clone()  # the kernel updates in place; never the caller's tensor
@@ -246,7 +268,7 @@ class ReplicaExchangeLangevin(_LadderSampler):
         spec_c = spec.to_c()
         if n > 0 and n_steps > 0:
             _lib.call(
-                "ebm_tempering_chain_f32",
+                entry,
                 spec_c, _lib.ptr(state), n, R, dim, n_steps, eta, eta**0.5, _lib.ptr(coef), _lib.ptr(beta),
                 self.swap_every, thin, _lib.ptr(traj) if need_kept else None, _lib.ptr(counts), None, None, seed, step0, stream,
             )
@@ -255,13 +277,18 @@ class ReplicaExchangeLangevin(_LadderSampler):
         if want_diag:
             diag = new_outputs(state, (n, dim), n_kept, False, True)[1]
             if n > 0 and n_kept > 0:
-                kept_statistics(spec_c, traj, diag, stream)
+                if spec.kind == _lib.ENERGY_MLP:  # the kept states' statistics in torch ops, their energy the model's
+                    for keep in range(n_kept):
+                        record_kept(traj[:, keep], keep, None, diag, lambda x_: self._model_energy(x_.contiguous(), {}))
+                else:
+                    kept_statistics(spec_c, traj, diag, stream)
             c = (counts.to(torch.int64) & 0xFFFFFFFF).to(torch.float64)  # (uint32 counters in an int32 tensor)
             diag["swap_acceptance"] = (c[R - 1 :] / c[: R - 1]).to(torch.float32)
         return state, (traj if want_traj else None), diag
 
 
-#: the ladder lengths of ``ebm_tempering_hmc_mlp_chain_f32`` (whole ladders per 32-row wave) and its widest row
+#: the ladder lengths of ``ebm_tempering_mlp_chain_f32`` and ``ebm_tempering_hmc_mlp_chain_f32`` (whole ladders per 32-row
+#: wave) and their widest row
 FUSED_MLP_LADDERS = (2, 4, 8, 16, 32)
 FUSED_MLP_MAX_DIM = 128
 
