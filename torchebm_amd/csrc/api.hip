@@ -154,6 +154,20 @@ int check_ladders(const ebm_energy_t* energy, const void* x, int64_t n_ladders, 
   return 0;
 }
 
+// What every entry that walks the MLP energy only checks first: the descriptor, then the kind (`twin` takes the analytic kinds)
+int check_mlp_walk(const ebm_energy_t* energy, int32_t dim, const char* who, const char* twin) {
+  if (int r = check_energy(energy, dim, who)) return r;
+  if (energy->kind != EBM_ENERGY_MLP) return fail(EBM_EKIND, "%s: this entry walks the MLP energy only (%s takes the analytic kinds)", who, twin);
+  return 0;
+}
+
+// The counted window of the four running-moments entries: two halves of h >= 2 steps behind the burn-in
+int check_moments_window(int32_t k_steps, int32_t burn_in, const char* who) {
+  if (k_steps < 0 || burn_in < 0 || burn_in > k_steps || ((k_steps - burn_in) & 1) || (k_steps - burn_in) / 2 < 2)
+    return fail(EBM_EINVAL, "%s: k_steps=%d burn_in=%d (k_steps - burn_in must be 2 h with h >= 2)", who, k_steps, burn_in);
+  return 0;
+}
+
 // ebm_langevin_chain_from_f32 on a kernel family that updates in place: the start state goes into the output first
 int copy_state(float* x, const float* src, size_t bytes, hipStream_t st, const char* who) {
   const hipError_t e = hipMemcpyAsync(x, src, bytes, hipMemcpyDeviceToDevice, st);
@@ -437,10 +451,8 @@ int ebm_tempering_mlp_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_
                                 int32_t swap_every, int32_t thin, float* traj, uint32_t* swap_counts, const float* noise,
                                 const float* u, uint64_t seed, uint64_t step0, void* stream) {
   const char* who = "ebm_tempering_mlp_chain_f32";
-  if (int r = check_energy(energy, dim, who)) return r;
-  if (energy->kind != EBM_ENERGY_MLP)
-    return fail(EBM_EKIND, "%s: this entry walks the MLP energy only (ebm_tempering_chain_f32 takes the analytic kinds)", who);
-  // (the dim range and the ladder lengths are tempering_mlp_check_shape's to refuse)
+  if (int r = check_mlp_walk(energy, dim, who, "ebm_tempering_chain_f32")) return r;
+  // (the dim range and the ladder lengths are wide_mlp_check_ladder_shape's to refuse)
   if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
   if (!noise_coef || !beta) return fail(EBM_EINVAL, "%s: noise_coef / beta is NULL", who);
   if (n_ladders < 0) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d, %d]", who, (long long)n_ladders, n_replicas, dim);
@@ -451,7 +463,7 @@ int ebm_tempering_mlp_chain_f32(const ebm_energy_t* energy, float* x, int64_t n_
     return fail(EBM_EINVAL, "%s: eta=%g sqrt_eta=%g (both must be finite)", who, (double)eta, (double)sqrt_eta);
   if (!aligned16(x) || (traj && !aligned16(traj)) || (noise && !aligned16(noise)))
     return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
-  if (int r = tempering_mlp_check_shape(energy->n_comp, dim, n_replicas)) return r;
+  if (int r = wide_mlp_check_ladder_shape(who, energy->n_comp, dim, n_replicas)) return r;
   if (n_ladders == 0) return 0;
   const TemperingChainReq q{*energy, x, n_ladders, n_replicas, dim, k_steps, eta, sqrt_eta, noise_coef, beta, swap_every, thin,
                             traj, swap_counts, noise, u, seed, step0};
@@ -484,10 +496,8 @@ int ebm_tempering_hmc_mlp_chain_f32(const ebm_energy_t* energy, float* x, int64_
                                     uint32_t* swap_counts, const float* p_noise, const float* u_accept, const float* u_swap,
                                     uint64_t seed, uint64_t step0, void* stream) {
   const char* who = "ebm_tempering_hmc_mlp_chain_f32";
-  if (int r = check_energy(energy, dim, who)) return r;
-  if (energy->kind != EBM_ENERGY_MLP)
-    return fail(EBM_EKIND, "%s: this entry walks the MLP energy only (ebm_tempering_hmc_chain_f32 takes the analytic kinds)", who);
-  // (the dim range and the ladder lengths are tempering_hmc_mlp_check_shape's to refuse)
+  if (int r = check_mlp_walk(energy, dim, who, "ebm_tempering_hmc_chain_f32")) return r;
+  // (the dim range and the ladder lengths are wide_mlp_check_ladder_shape's to refuse)
   if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
   if (!eps || !sqrt_temp || !beta) return fail(EBM_EINVAL, "%s: eps / sqrt_temp / beta is NULL", who);
   if (n_ladders < 0) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d, %d]", who, (long long)n_ladders, n_replicas, dim);
@@ -498,7 +508,7 @@ int ebm_tempering_hmc_mlp_chain_f32(const ebm_energy_t* energy, float* x, int64_
     return fail(EBM_EINVAL, "%s: p_noise, u_accept and u_swap must be given together", who);
   if (!aligned16(x) || (traj && !aligned16(traj)) || (p_noise && !aligned16(p_noise)))
     return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
-  if (int r = tempering_hmc_mlp_check_shape(energy->n_comp, dim, n_replicas)) return r;
+  if (int r = wide_mlp_check_ladder_shape(who, energy->n_comp, dim, n_replicas)) return r;
   if (n_ladders == 0) return 0;
   const TemperingHmcChainReq q{*energy, x, n_ladders, n_replicas, dim, n_mh, n_leapfrog, eps, sqrt_temp, beta, swap_every, thin,
                                traj, accept_mask, accept_counts, swap_counts, p_noise, u_accept, u_swap, seed, step0};
@@ -512,11 +522,9 @@ static int ais_chain_impl(const char* who, bool mlp, const ebm_energy_t* energy,
                           uint64_t seed, uint64_t step0, void* stream) {
   if (!mlp && energy && energy->kind == EBM_ENERGY_MLP)
     return fail(EBM_EKIND, "%s: the MLP energy has no annealed-importance-sampling kernel (the sampler's eager route takes it)", who);
-  if (int r = check_energy(energy, dim, who)) return r;
-  if (mlp && energy->kind != EBM_ENERGY_MLP)
-    return fail(EBM_EKIND, "%s: this entry walks the MLP energy only (ebm_ais_chain_f32 takes the analytic kinds)", who);
+  if (int r = mlp ? check_mlp_walk(energy, dim, who, "ebm_ais_chain_f32") : check_energy(energy, dim, who)) return r;
   if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
-  // (the MLP walk's dim range is ais_mlp_check_shape's to refuse)
+  // (the MLP walk's dim range is wide_mlp_check_shape's to refuse)
   if (n_chains < 0 || (!mlp && dim < 1)) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d]", who, (long long)n_chains, dim);
   if (!aligned16(x)) return fail(EBM_EINVAL, "%s: state pointer must be 16-byte aligned", who);
   if (!logw) return fail(EBM_EINVAL, "%s: logw is NULL", who);
@@ -527,7 +535,7 @@ static int ais_chain_impl(const char* who, bool mlp, const ebm_energy_t* energy,
   if ((x0 == nullptr) != (p_noise == nullptr) || (x0 == nullptr) != (u_accept == nullptr))
     return fail(EBM_EINVAL, "%s: x0, p_noise and u_accept must be given together", who);
   if (mlp)
-    if (int r = ais_mlp_check_shape(energy->n_comp, dim)) return r;
+    if (int r = wide_mlp_check_shape(who, energy->n_comp, dim)) return r;
   if (n_chains == 0) return 0;
   if ((x0 && !aligned16(x0)) || (p_noise && !aligned16(p_noise))) return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
   const AisChainReq q{*energy, x, logw, n_chains, dim, n_temps, n_leapfrog, beta, eps, sigma0, inv_var0, accept_mask, accept_counts,
@@ -563,8 +571,7 @@ int ebm_chain_moments_f32(const ebm_energy_t* energy, float* x, int64_t n_chains
   if (int r = check_state(x, n_chains, dim, who)) return r;
   if (sampler != 0 && sampler != 1) return fail(EBM_EINVAL, "%s: sampler=%d (0 = Langevin, 1 = HMC)", who, sampler);
   const bool hmc = sampler == 1;
-  if (k_steps < 0 || burn_in < 0 || burn_in > k_steps || ((k_steps - burn_in) & 1) || (k_steps - burn_in) / 2 < 2)
-    return fail(EBM_EINVAL, "%s: k_steps=%d burn_in=%d (k_steps - burn_in must be 2 h with h >= 2)", who, k_steps, burn_in);
+  if (int r = check_moments_window(k_steps, burn_in, who)) return r;
   if (hmc && n_leapfrog < 1) return fail(EBM_EINVAL, "%s: n_leapfrog=%d", who, n_leapfrog);
   if (int r = moments_check_geometry(dim)) return r;
   if (!recip || !mom) return fail(EBM_EINVAL, "%s: recip / mom is NULL", who);
@@ -585,22 +592,19 @@ int ebm_chain_moments_mlp_f32(const ebm_energy_t* energy, float* x, int64_t n_ch
                               void* stream) {
   const char* who = "ebm_chain_moments_mlp_f32";
   (void)n_leapfrog; (void)eps; (void)accept_mask; (void)accept_count; (void)u;  // the HMC half of the shared parameter list
-  if (int r = check_energy(energy, dim, who)) return r;
-  if (energy->kind != EBM_ENERGY_MLP)
-    return fail(EBM_EKIND, "%s: this entry walks the MLP energy only (ebm_chain_moments_f32 takes the analytic kinds)", who);
-  // (the dim range is langevin_moments_mlp_check_shape's to refuse)
+  if (int r = check_mlp_walk(energy, dim, who, "ebm_chain_moments_f32")) return r;
+  // (the dim range is wide_mlp_check_shape's to refuse)
   if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
   if (n_chains < 0) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d]", who, (long long)n_chains, dim);
   if (sampler != 0)
     return fail(EBM_EINVAL, "%s: sampler=%d (0 = Langevin; for HMC on the MLP: ebm_kinetic_moments_mlp_f32, generalized HMC at infinite friction)",
                 who, sampler);
-  if (k_steps < 0 || burn_in < 0 || burn_in > k_steps || ((k_steps - burn_in) & 1) || (k_steps - burn_in) / 2 < 2)
-    return fail(EBM_EINVAL, "%s: k_steps=%d burn_in=%d (k_steps - burn_in must be 2 h with h >= 2)", who, k_steps, burn_in);
+  if (int r = check_moments_window(k_steps, burn_in, who)) return r;
   if (!std::isfinite(eta) || !std::isfinite(sqrt_eta) || !std::isfinite(noise_coef))
     return fail(EBM_EINVAL, "%s: eta=%g sqrt_eta=%g noise_coef=%g (all must be finite)", who, (double)eta, (double)sqrt_eta,
                 (double)noise_coef);
   if (!recip || !mom) return fail(EBM_EINVAL, "%s: recip / mom is NULL", who);
-  if (int r = langevin_moments_mlp_check_shape(energy->n_comp, dim)) return r;
+  if (int r = wide_mlp_check_shape(who, energy->n_comp, dim)) return r;
   if (n_chains == 0) return 0;
   if (!aligned16(x) || !aligned16(mom) || (traj && !aligned16(traj)) || (noise && !aligned16(noise)))
     return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
@@ -620,48 +624,46 @@ static KineticChainReq kinetic_request(const ebm_energy_t* energy, float* x, flo
   return KineticChainReq{*energy, x, v, n_chains, dim, k_steps, hh, c1, c2, sqrt_temp, draw_v0 != 0, thin, traj, noise, seed, offset};
 }
 
-int ebm_kinetic_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t k_steps,
-                          double h, double gamma, double temperature, int32_t draw_v0, int32_t thin, float* traj,
-                          const float* noise, uint64_t seed, uint64_t offset, void* stream) {
-  const char* who = "ebm_kinetic_chain_f32";
-  if (energy && energy->kind == EBM_ENERGY_MLP)
+// Both underdamped-Langevin entries: the analytic kinds on the lane-group kernel, the MLP energy on the matrix cores.  The analytic
+// entry refuses dim < 1 and a misaligned x with its state; the MLP entry leaves the dim range to wide_mlp_check_shape and checks
+// every pointer's alignment behind the empty call.
+static int kinetic_chain_impl(const char* who, bool mlp, const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim,
+                              int32_t k_steps, double h, double gamma, double temperature, int32_t draw_v0, int32_t thin, float* traj,
+                              const float* noise, uint64_t seed, uint64_t offset, void* stream) {
+  if (!mlp && energy && energy->kind == EBM_ENERGY_MLP)
     return fail(EBM_EKIND, "%s: the MLP energy has no underdamped-Langevin kernel (the sampler's eager route takes it)", who);
-  if (int r = check_energy(energy, dim, who)) return r;
-  if (int r = check_state(x, n_chains, dim, who)) return r;
+  if (int r = mlp ? check_mlp_walk(energy, dim, who, "ebm_kinetic_chain_f32") : check_energy(energy, dim, who)) return r;
+  if (!mlp) {
+    if (int r = check_state(x, n_chains, dim, who)) return r;
+  } else if (!x) {
+    return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
+  }
   if (!v) return fail(EBM_EINVAL, "%s: velocity pointer is NULL", who);
+  if (mlp && n_chains < 0) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d]", who, (long long)n_chains, dim);
   if (k_steps < 1 || thin < 1) return fail(EBM_EINVAL, "%s: k_steps=%d thin=%d (both must be >= 1)", who, k_steps, thin);
   if (!(h > 0.0) || !(gamma > 0.0) || !(temperature > 0.0) || !std::isfinite(h) || !std::isfinite(gamma) || !std::isfinite(temperature))
     return fail(EBM_EINVAL, "%s: h=%g gamma=%g temperature=%g (all must be positive and finite)", who, h, gamma, temperature);
-  if (int r = kinetic_check_geometry(dim)) return r;
+  if (int r = mlp ? wide_mlp_check_shape(who, energy->n_comp, dim) : kinetic_check_geometry(dim)) return r;
   if (n_chains == 0) return 0;
-  if (!aligned16(v) || (traj && !aligned16(traj)) || (noise && !aligned16(noise)))
+  if ((mlp && !aligned16(x)) || !aligned16(v) || (traj && !aligned16(traj)) || (noise && !aligned16(noise)))
     return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
-  return kinetic_chain_launch(kinetic_request(energy, x, v, n_chains, dim, k_steps, h, gamma, temperature, draw_v0, thin, traj, noise,
-                                              seed, offset),
-                              (hipStream_t)stream);
+  const KineticChainReq q = kinetic_request(energy, x, v, n_chains, dim, k_steps, h, gamma, temperature, draw_v0, thin, traj, noise,
+                                            seed, offset);
+  return mlp ? kinetic_mlp_chain_launch(q, (hipStream_t)stream) : kinetic_chain_launch(q, (hipStream_t)stream);
+}
+
+int ebm_kinetic_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t k_steps,
+                          double h, double gamma, double temperature, int32_t draw_v0, int32_t thin, float* traj,
+                          const float* noise, uint64_t seed, uint64_t offset, void* stream) {
+  return kinetic_chain_impl("ebm_kinetic_chain_f32", false, energy, x, v, n_chains, dim, k_steps, h, gamma, temperature, draw_v0, thin,
+                            traj, noise, seed, offset, stream);
 }
 
 int ebm_kinetic_mlp_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t k_steps,
                               double h, double gamma, double temperature, int32_t draw_v0, int32_t thin, float* traj,
                               const float* noise, uint64_t seed, uint64_t offset, void* stream) {
-  const char* who = "ebm_kinetic_mlp_chain_f32";
-  if (int r = check_energy(energy, dim, who)) return r;
-  if (energy->kind != EBM_ENERGY_MLP)
-    return fail(EBM_EKIND, "%s: this entry walks the MLP energy only (ebm_kinetic_chain_f32 takes the analytic kinds)", who);
-  // (the dim range is kinetic_mlp_check_shape's to refuse)
-  if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
-  if (!v) return fail(EBM_EINVAL, "%s: velocity pointer is NULL", who);
-  if (n_chains < 0) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d]", who, (long long)n_chains, dim);
-  if (k_steps < 1 || thin < 1) return fail(EBM_EINVAL, "%s: k_steps=%d thin=%d (both must be >= 1)", who, k_steps, thin);
-  if (!(h > 0.0) || !(gamma > 0.0) || !(temperature > 0.0) || !std::isfinite(h) || !std::isfinite(gamma) || !std::isfinite(temperature))
-    return fail(EBM_EINVAL, "%s: h=%g gamma=%g temperature=%g (all must be positive and finite)", who, h, gamma, temperature);
-  if (int r = kinetic_mlp_check_shape(energy->n_comp, dim)) return r;
-  if (n_chains == 0) return 0;
-  if (!aligned16(x) || !aligned16(v) || (traj && !aligned16(traj)) || (noise && !aligned16(noise)))
-    return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
-  return kinetic_mlp_chain_launch(kinetic_request(energy, x, v, n_chains, dim, k_steps, h, gamma, temperature, draw_v0, thin, traj,
-                                                  noise, seed, offset),
-                                  (hipStream_t)stream);
+  return kinetic_chain_impl("ebm_kinetic_mlp_chain_f32", true, energy, x, v, n_chains, dim, k_steps, h, gamma, temperature, draw_v0,
+                            thin, traj, noise, seed, offset, stream);
 }
 
 // The request of both generalized-HMC entries: the constants of the refresh over one trajectory's time eps L, formed in double,
@@ -679,6 +681,19 @@ static GhmcChainReq ghmc_request(const ebm_energy_t* energy, float* x, float* v,
                       accept_mask, noise, u, seed, offset};
 }
 
+// What both generalized-HMC entries ask of the step counts and of the walk's parameters, adjacent in both
+// (gamma = +inf is allowed: a full refresh, the HMC transition)
+static int check_ghmc_parameters(int32_t n_mh, int32_t n_leapfrog, int32_t thin, double eps, double gamma, double temperature,
+                                 const char* who) {
+  if (n_mh < 1 || n_leapfrog < 1 || thin < 1)
+    return fail(EBM_EINVAL, "%s: n_mh=%d n_leapfrog=%d thin=%d (all must be >= 1)", who, n_mh, n_leapfrog, thin);
+  if (!(eps > 0.0) || !(gamma > 0.0) || !(temperature > 0.0) || !std::isfinite(eps) || !std::isfinite(temperature))
+    return fail(EBM_EINVAL, "%s: eps=%g gamma=%g temperature=%g (all must be positive; eps and temperature finite)", who, eps, gamma,
+                temperature);
+  return 0;
+}
+
+// (two entries, not one impl: each forms its request in its own body, where tests/test_ghmc_mlp.py reads it)
 int ebm_ghmc_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t n_mh,
                        int32_t n_leapfrog, double eps, double gamma, double temperature, int32_t draw_v0, int32_t thin,
                        float* traj, uint8_t* accept_mask, const float* noise, const float* u, uint64_t seed, uint64_t offset,
@@ -690,12 +705,7 @@ int ebm_ghmc_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n
   if (int r = ghmc_check_geometry(dim)) return r;  // (in front of check_state: dim < 1 is EBM_EDIM here, as dim > 256 is)
   if (int r = check_state(x, n_chains, dim, who)) return r;
   if (!v) return fail(EBM_EINVAL, "%s: velocity pointer is NULL", who);
-  if (n_mh < 1 || n_leapfrog < 1 || thin < 1)
-    return fail(EBM_EINVAL, "%s: n_mh=%d n_leapfrog=%d thin=%d (all must be >= 1)", who, n_mh, n_leapfrog, thin);
-  // (gamma = +inf is allowed: a full refresh, the HMC transition)
-  if (!(eps > 0.0) || !(gamma > 0.0) || !(temperature > 0.0) || !std::isfinite(eps) || !std::isfinite(temperature))
-    return fail(EBM_EINVAL, "%s: eps=%g gamma=%g temperature=%g (all must be positive; eps and temperature finite)", who, eps, gamma,
-                temperature);
+  if (int r = check_ghmc_parameters(n_mh, n_leapfrog, thin, eps, gamma, temperature, who)) return r;
   if (n_chains == 0) return 0;
   if (!aligned16(v) || (traj && !aligned16(traj)) || (noise && !aligned16(noise)))
     return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
@@ -709,20 +719,13 @@ int ebm_ghmc_mlp_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64
                            float* traj, uint8_t* accept_mask, const float* noise, const float* u, uint64_t seed, uint64_t offset,
                            void* stream) {
   const char* who = "ebm_ghmc_mlp_chain_f32";
-  if (int r = check_energy(energy, dim, who)) return r;
-  if (energy->kind != EBM_ENERGY_MLP)
-    return fail(EBM_EKIND, "%s: this entry walks the MLP energy only (ebm_ghmc_chain_f32 takes the analytic kinds)", who);
-  // (the dim range is ghmc_mlp_check_shape's to refuse)
+  if (int r = check_mlp_walk(energy, dim, who, "ebm_ghmc_chain_f32")) return r;
+  // (the dim range is wide_mlp_check_shape's to refuse)
   if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
   if (!v) return fail(EBM_EINVAL, "%s: velocity pointer is NULL", who);
   if (n_chains < 0) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d]", who, (long long)n_chains, dim);
-  if (n_mh < 1 || n_leapfrog < 1 || thin < 1)
-    return fail(EBM_EINVAL, "%s: n_mh=%d n_leapfrog=%d thin=%d (all must be >= 1)", who, n_mh, n_leapfrog, thin);
-  // (gamma = +inf is allowed: a full refresh, the HMC transition)
-  if (!(eps > 0.0) || !(gamma > 0.0) || !(temperature > 0.0) || !std::isfinite(eps) || !std::isfinite(temperature))
-    return fail(EBM_EINVAL, "%s: eps=%g gamma=%g temperature=%g (all must be positive; eps and temperature finite)", who, eps, gamma,
-                temperature);
-  if (int r = ghmc_mlp_check_shape(energy->n_comp, dim)) return r;
+  if (int r = check_ghmc_parameters(n_mh, n_leapfrog, thin, eps, gamma, temperature, who)) return r;
+  if (int r = wide_mlp_check_shape(who, energy->n_comp, dim)) return r;
   if (n_chains == 0) return 0;
   if (!aligned16(x) || !aligned16(v) || (traj && !aligned16(traj)) || (noise && !aligned16(noise)))
     return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
@@ -731,22 +734,28 @@ int ebm_ghmc_mlp_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64
                                (hipStream_t)stream);
 }
 
-int ebm_kinetic_moments_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t sampler,
-                            int32_t k_steps, int32_t burn_in, int32_t n_leapfrog, double step, double gamma, double temperature,
-                            int32_t draw_v0, const float* recip, float* mom, float* e_mom, float* v2_mom, float* traj,
-                            float* e_traj, float* v_traj, uint8_t* accept_mask, uint32_t* accept_count, const float* noise,
-                            const float* u, uint64_t seed, uint64_t offset, void* stream) {
-  const char* who = "ebm_kinetic_moments_f32";
-  if (energy && energy->kind == EBM_ENERGY_MLP)
+// Both running-moments entries of the two walkers, as the underdamped pair; the analytic entry's geometry stands in front of its
+// state (dim < 1 is EBM_EDIM there, as dim > 256 is)
+static int kinetic_moments_impl(const char* who, bool mlp, const ebm_energy_t* energy, float* x, float* v, int64_t n_chains,
+                                int32_t dim, int32_t sampler, int32_t k_steps, int32_t burn_in, int32_t n_leapfrog, double step,
+                                double gamma, double temperature, int32_t draw_v0, const float* recip, float* mom, float* e_mom,
+                                float* v2_mom, float* traj, float* e_traj, float* v_traj, uint8_t* accept_mask,
+                                uint32_t* accept_count, const float* noise, const float* u, uint64_t seed, uint64_t offset,
+                                void* stream) {
+  if (!mlp && energy && energy->kind == EBM_ENERGY_MLP)
     return fail(EBM_EKIND, "%s: the MLP energy has no running-moments kernel (the samplers' eager route takes it)", who);
-  if (int r = check_energy(energy, dim, who)) return r;
-  if (int r = kinetic_moments_check_geometry(dim)) return r;  // (in front of check_state: dim < 1 is EBM_EDIM here, as dim > 256 is)
-  if (int r = check_state(x, n_chains, dim, who)) return r;
+  if (int r = mlp ? check_mlp_walk(energy, dim, who, "ebm_kinetic_moments_f32") : check_energy(energy, dim, who)) return r;
+  if (!mlp) {
+    if (int r = kinetic_moments_check_geometry(dim)) return r;
+    if (int r = check_state(x, n_chains, dim, who)) return r;
+  } else if (!x) {
+    return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
+  }
   if (!v) return fail(EBM_EINVAL, "%s: velocity pointer is NULL", who);
+  if (mlp && n_chains < 0) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d]", who, (long long)n_chains, dim);
   if (sampler != 0 && sampler != 1) return fail(EBM_EINVAL, "%s: sampler=%d (0 = BAOAB, 1 = GHMC)", who, sampler);
   const bool ghmc = sampler == 1;
-  if (k_steps < 0 || burn_in < 0 || burn_in > k_steps || ((k_steps - burn_in) & 1) || (k_steps - burn_in) / 2 < 2)
-    return fail(EBM_EINVAL, "%s: k_steps=%d burn_in=%d (k_steps - burn_in must be 2 h with h >= 2)", who, k_steps, burn_in);
+  if (int r = check_moments_window(k_steps, burn_in, who)) return r;
   // (GHMC: gamma = +inf is allowed, a full refresh)
   if (!(step > 0.0) || !(gamma > 0.0) || !(temperature > 0.0) || !std::isfinite(step) || !std::isfinite(temperature) ||
       (!ghmc && !std::isfinite(gamma)))
@@ -755,29 +764,38 @@ int ebm_kinetic_moments_f32(const ebm_energy_t* energy, float* x, float* v, int6
   if (ghmc && n_leapfrog < 1) return fail(EBM_EINVAL, "%s: n_leapfrog=%d", who, n_leapfrog);
   if (ghmc && (v2_mom || v_traj)) return fail(EBM_EINVAL, "%s: v2_mom / v_traj are BAOAB outputs (sampler = 0)", who);
   if (!recip || !mom) return fail(EBM_EINVAL, "%s: recip / mom is NULL", who);
+  if (mlp)
+    if (int r = wide_mlp_check_shape(who, energy->n_comp, dim)) return r;
   if (n_chains == 0) return 0;
-  if (!aligned16(v) || !aligned16(mom) || (v2_mom && !aligned16(v2_mom)) || (traj && !aligned16(traj)) ||
+  if ((mlp && !aligned16(x)) || !aligned16(v) || !aligned16(mom) || (v2_mom && !aligned16(v2_mom)) || (traj && !aligned16(traj)) ||
       (v_traj && !aligned16(v_traj)) || (noise && !aligned16(noise)))
     return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
-  // the constants of either walker, as its chain entry forms them: in double, each rounded once
-  const float sqrt_temp = (float)sqrt(temperature);
-  float hh = 0.0f, eps = 0.0f, c1, c2, beta = 0.0f;
+  // the walkers' constants by the host code of the two plain entries
+  const auto launch = mlp ? kinetic_moments_mlp_chain_launch : kinetic_moments_chain_launch;
   if (ghmc) {
-    const double span = gamma * step * (double)n_leapfrog;
-    eps = (float)step;
-    c1 = std::isinf(gamma) ? 0.0f : (float)exp(-span);
-    c2 = std::isinf(gamma) ? sqrt_temp : (float)sqrt(temperature * (-expm1(-2.0 * span)));
-    beta = (float)(1.0 / temperature);
-  } else {
-    hh = (float)(0.5 * step);
-    c1 = (float)exp(-gamma * step);
-    c2 = (float)sqrt(temperature * (-expm1(-2.0 * gamma * step)));
+    const GhmcChainReq g = ghmc_request(energy, x, v, n_chains, dim, k_steps, n_leapfrog, step, gamma, temperature, draw_v0, 1,
+                                        nullptr, accept_mask, noise, u, seed, offset);
+    const KineticMomentsChainReq q{*energy, x, v, n_chains, dim, true, k_steps, burn_in, n_leapfrog, 0.0f, g.eps, g.c1, g.c2,
+                                   g.sqrt_temp, g.beta, draw_v0 != 0, recip, mom, e_mom, nullptr, traj, e_traj, nullptr,
+                                   accept_mask, accept_count, noise, u, seed, offset};
+    return launch(q, (hipStream_t)stream);
   }
-  const KineticMomentsChainReq q{*energy, x, v, n_chains, dim, ghmc, k_steps, burn_in, n_leapfrog, hh, eps, c1, c2, sqrt_temp,
-                                 beta, draw_v0 != 0, recip, mom, e_mom, ghmc ? nullptr : v2_mom, traj, e_traj,
-                                 ghmc ? nullptr : v_traj, ghmc ? accept_mask : nullptr, ghmc ? accept_count : nullptr, noise,
-                                 ghmc ? u : nullptr, seed, offset};
-  return kinetic_moments_chain_launch(q, (hipStream_t)stream);
+  const KineticChainReq b = kinetic_request(energy, x, v, n_chains, dim, k_steps, step, gamma, temperature, draw_v0, 1, nullptr,
+                                            noise, seed, offset);
+  const KineticMomentsChainReq q{*energy, x, v, n_chains, dim, false, k_steps, burn_in, n_leapfrog, b.hh, 0.0f, b.c1, b.c2,
+                                 b.sqrt_temp, 0.0f, draw_v0 != 0, recip, mom, e_mom, v2_mom, traj, e_traj, v_traj, nullptr, nullptr,
+                                 noise, nullptr, seed, offset};
+  return launch(q, (hipStream_t)stream);
+}
+
+int ebm_kinetic_moments_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t sampler,
+                            int32_t k_steps, int32_t burn_in, int32_t n_leapfrog, double step, double gamma, double temperature,
+                            int32_t draw_v0, const float* recip, float* mom, float* e_mom, float* v2_mom, float* traj,
+                            float* e_traj, float* v_traj, uint8_t* accept_mask, uint32_t* accept_count, const float* noise,
+                            const float* u, uint64_t seed, uint64_t offset, void* stream) {
+  return kinetic_moments_impl("ebm_kinetic_moments_f32", false, energy, x, v, n_chains, dim, sampler, k_steps, burn_in, n_leapfrog,
+                              step, gamma, temperature, draw_v0, recip, mom, e_mom, v2_mom, traj, e_traj, v_traj, accept_mask,
+                              accept_count, noise, u, seed, offset, stream);
 }
 
 int ebm_kinetic_moments_mlp_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t sampler,
@@ -785,46 +803,9 @@ int ebm_kinetic_moments_mlp_f32(const ebm_energy_t* energy, float* x, float* v, 
                                 double temperature, int32_t draw_v0, const float* recip, float* mom, float* e_mom, float* v2_mom,
                                 float* traj, float* e_traj, float* v_traj, uint8_t* accept_mask, uint32_t* accept_count,
                                 const float* noise, const float* u, uint64_t seed, uint64_t offset, void* stream) {
-  const char* who = "ebm_kinetic_moments_mlp_f32";
-  if (int r = check_energy(energy, dim, who)) return r;
-  if (energy->kind != EBM_ENERGY_MLP)
-    return fail(EBM_EKIND, "%s: this entry walks the MLP energy only (ebm_kinetic_moments_f32 takes the analytic kinds)", who);
-  // (the dim range is kinetic_moments_mlp_check_shape's to refuse)
-  if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
-  if (!v) return fail(EBM_EINVAL, "%s: velocity pointer is NULL", who);
-  if (n_chains < 0) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d]", who, (long long)n_chains, dim);
-  if (sampler != 0 && sampler != 1) return fail(EBM_EINVAL, "%s: sampler=%d (0 = BAOAB, 1 = GHMC)", who, sampler);
-  const bool ghmc = sampler == 1;
-  if (k_steps < 0 || burn_in < 0 || burn_in > k_steps || ((k_steps - burn_in) & 1) || (k_steps - burn_in) / 2 < 2)
-    return fail(EBM_EINVAL, "%s: k_steps=%d burn_in=%d (k_steps - burn_in must be 2 h with h >= 2)", who, k_steps, burn_in);
-  // (GHMC: gamma = +inf is allowed, a full refresh)
-  if (!(step > 0.0) || !(gamma > 0.0) || !(temperature > 0.0) || !std::isfinite(step) || !std::isfinite(temperature) ||
-      (!ghmc && !std::isfinite(gamma)))
-    return fail(EBM_EINVAL, "%s: step=%g gamma=%g temperature=%g (all must be positive; finite, but for GHMC's gamma)", who, step,
-                gamma, temperature);
-  if (ghmc && n_leapfrog < 1) return fail(EBM_EINVAL, "%s: n_leapfrog=%d", who, n_leapfrog);
-  if (ghmc && (v2_mom || v_traj)) return fail(EBM_EINVAL, "%s: v2_mom / v_traj are BAOAB outputs (sampler = 0)", who);
-  if (!recip || !mom) return fail(EBM_EINVAL, "%s: recip / mom is NULL", who);
-  if (int r = kinetic_moments_mlp_check_shape(energy->n_comp, dim)) return r;
-  if (n_chains == 0) return 0;
-  if (!aligned16(x) || !aligned16(v) || !aligned16(mom) || (v2_mom && !aligned16(v2_mom)) || (traj && !aligned16(traj)) ||
-      (v_traj && !aligned16(v_traj)) || (noise && !aligned16(noise)))
-    return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
-  // the walkers' constants by the host code of the two plain MLP entries
-  if (ghmc) {
-    const GhmcChainReq g = ghmc_request(energy, x, v, n_chains, dim, k_steps, n_leapfrog, step, gamma, temperature, draw_v0, 1,
-                                        nullptr, accept_mask, noise, u, seed, offset);
-    const KineticMomentsChainReq q{*energy, x, v, n_chains, dim, true, k_steps, burn_in, n_leapfrog, 0.0f, g.eps, g.c1, g.c2,
-                                   g.sqrt_temp, g.beta, draw_v0 != 0, recip, mom, e_mom, nullptr, traj, e_traj, nullptr,
-                                   accept_mask, accept_count, noise, u, seed, offset};
-    return kinetic_moments_mlp_chain_launch(q, (hipStream_t)stream);
-  }
-  const KineticChainReq b = kinetic_request(energy, x, v, n_chains, dim, k_steps, step, gamma, temperature, draw_v0, 1, nullptr,
-                                            noise, seed, offset);
-  const KineticMomentsChainReq q{*energy, x, v, n_chains, dim, false, k_steps, burn_in, n_leapfrog, b.hh, 0.0f, b.c1, b.c2,
-                                 b.sqrt_temp, 0.0f, draw_v0 != 0, recip, mom, e_mom, v2_mom, traj, e_traj, v_traj, nullptr, nullptr,
-                                 noise, nullptr, seed, offset};
-  return kinetic_moments_mlp_chain_launch(q, (hipStream_t)stream);
+  return kinetic_moments_impl("ebm_kinetic_moments_mlp_f32", true, energy, x, v, n_chains, dim, sampler, k_steps, burn_in,
+                              n_leapfrog, step, gamma, temperature, draw_v0, recip, mom, e_mom, v2_mom, traj, e_traj, v_traj,
+                              accept_mask, accept_count, noise, u, seed, offset, stream);
 }
 
 int ebm_leapfrog_kick_drift_f32(const float* x, const float* p, const float* force, float* x_new,

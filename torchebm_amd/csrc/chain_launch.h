@@ -318,14 +318,34 @@ int launch_hmc_chain_matrix_diag(const HmcChainReq&, hipStream_t);  // matrix_hm
 bool matrix_hmc_diag_plan(const ebm_energy_t&, int64_t n_chains, int32_t dim, diag::DiagArgs&);
 
 // ---------------------------------------------------------------------------------
+// The walks on the wide MLP energy (mlp_wide_*.hip; the ... on the MLP energy launchers below)
+// ---------------------------------------------------------------------------------
+// Which MLP shapes the fused walks take, said once: 0, or the refusal under the entry's name `who` (hidden width not 64 / 128,
+// dim outside 1 .. 128).  No launch and no device access: an entry calls it in front of its early return for an empty call, so
+// it needs no GPU; the launcher calls it again.  (samplers/_chain_host.py, fused_mlp_walk_fits, is the Python form.)
+inline int wide_mlp_check_shape(const char* who, int32_t hidden, int32_t dim) {
+  if ((hidden != 64 && hidden != 128) || dim < 1 || dim > 128)
+    return fail(EBM_EDIM, "%s: the fused MLP walk supports hidden width 64 or 128 and 1 <= dim <= 128 (got %d, %d)", who, hidden, dim);
+  return 0;
+}
+// ... of the tempered walks, whose waves hold whole ladders: and n_replicas not in {2, 4, 8, 16, 32}
+inline int wide_mlp_check_ladder_shape(const char* who, int32_t hidden, int32_t dim, int32_t n_replicas) {
+  const bool ladder_ok = n_replicas == 2 || n_replicas == 4 || n_replicas == 8 || n_replicas == 16 || n_replicas == 32;
+  if ((hidden != 64 && hidden != 128) || dim < 1 || dim > 128 || !ladder_ok)
+    return fail(EBM_EDIM,
+                "%s: the fused MLP ladder supports hidden width 64 or 128, 1 <= dim <= 128 and 2, 4, 8, 16 or 32 replicas "
+                "(got %d, %d, %d)",
+                who, hidden, dim, n_replicas);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------
 // Replica-exchange Langevin (tempering.hip: a ladder of tempered walkers per chain, swaps inside the launch)
 // ---------------------------------------------------------------------------------
 int tempering_chain_launch(const TemperingChainReq&, hipStream_t);
 int tempering_check_geometry(int32_t n_replicas, int32_t dim);  // 0, or the refusal (dim > 1024, ladder wider than a workgroup)
 // ... on the MLP energy (mlp_wide_tempering_langevin.hip: the same request; 32 slot rows per wave around the matrix-core evaluation, one per step, a swap moves state and gradient between neighbouring lanes)
 int tempering_mlp_chain_launch(const TemperingChainReq&, hipStream_t);
-// 0, or the refusal (hidden width not 64 / 128, dim outside 1 .. 128, n_replicas not in {2, 4, 8, 16, 32})
-int tempering_mlp_check_shape(int32_t hidden, int32_t dim, int32_t n_replicas);
 
 // ---------------------------------------------------------------------------------
 // Replica-exchange HMC (tempering_hmc.hip: the same ladders, a Metropolis-corrected HMC transition in every slot)
@@ -334,8 +354,6 @@ int tempering_hmc_chain_launch(const TemperingHmcChainReq&, hipStream_t);
 int tempering_hmc_check_geometry(int32_t n_replicas, int32_t dim);  // 0, or the refusal (dim > 256, ladder wider than a workgroup)
 // ... on the MLP energy (mlp_wide_tempering.hip: the same request; 32 slot rows per wave around the matrix-core evaluation, n_leapfrog + 1 of them per transition, a swap moves the states between neighbouring lanes)
 int tempering_hmc_mlp_chain_launch(const TemperingHmcChainReq&, hipStream_t);
-// 0, or the refusal (hidden width not 64 / 128, dim outside 1 .. 128, n_replicas not in {2, 4, 8, 16, 32})
-int tempering_hmc_mlp_check_shape(int32_t hidden, int32_t dim, int32_t n_replicas);
 
 // ---------------------------------------------------------------------------------
 // Annealed importance sampling (ais.hip: one walker per chain through the temperatures in time, the weight from carried energies)
@@ -344,7 +362,6 @@ int ais_chain_launch(const AisChainReq&, hipStream_t);
 int ais_check_geometry(int32_t dim);  // 0, or the refusal (dim > 256)
 // ... on the MLP energy (mlp_wide_ais.hip: the same request; 32 chains per wave around the matrix-core evaluation, n_leapfrog + 1 of them per transition)
 int ais_mlp_chain_launch(const AisChainReq&, hipStream_t);
-int ais_mlp_check_shape(int32_t hidden, int32_t dim);  // 0, or the refusal (hidden width not 64 / 128, dim outside 1 .. 128)
 
 
 // ---------------------------------------------------------------------------------
@@ -354,7 +371,6 @@ int moments_chain_launch(const MomentsChainReq&, hipStream_t);
 int moments_check_geometry(int32_t dim);  // 0, or the refusal (dim > 256)
 // ... of the Langevin walker on the MLP energy (mlp_wide_langevin_moments.hip: 32 chains per wave around the matrix-core evaluation, k_steps of them per call and one more with energies, the Welford pairs kept in the caller's planes)
 int langevin_moments_mlp_chain_launch(const LangevinMomentsChainReq&, hipStream_t);
-int langevin_moments_mlp_check_shape(int32_t hidden, int32_t dim);  // 0, or the refusal (hidden width not 64 / 128, dim outside 1 .. 128)
 
 // ---------------------------------------------------------------------------------
 // Underdamped Langevin, BAOAB (kinetic.hip: a walker per chain with position, velocity and carried gradient in registers)
@@ -363,7 +379,6 @@ int kinetic_chain_launch(const KineticChainReq&, hipStream_t);
 int kinetic_check_geometry(int32_t dim);  // 0, or the refusal (dim > 256)
 // ... on the MLP energy (mlp_wide_kinetic.hip: the same request; 32 chains per wave around the matrix-core evaluation, k_steps + 1 of them per call)
 int kinetic_mlp_chain_launch(const KineticChainReq&, hipStream_t);
-int kinetic_mlp_check_shape(int32_t hidden, int32_t dim);  // 0, or the refusal (hidden width not 64 / 128, dim outside 1 .. 128)
 
 // ---------------------------------------------------------------------------------
 // Generalized HMC (ghmc.hip: the kinetic walker with a partial momentum refresh, a Metropolis-corrected trajectory and the flip)
@@ -372,7 +387,6 @@ int ghmc_chain_launch(const GhmcChainReq&, hipStream_t);
 int ghmc_check_geometry(int32_t dim);  // 0, or the refusal (dim > 256)
 // ... on the MLP energy (mlp_wide_ghmc.hip: the same request; 32 chains per wave around the matrix-core evaluation, n_leapfrog + 1 of them per transition)
 int ghmc_mlp_chain_launch(const GhmcChainReq&, hipStream_t);
-int ghmc_mlp_check_shape(int32_t hidden, int32_t dim);  // 0, or the refusal (hidden width not 64 / 128, dim outside 1 .. 128)
 
 // ---------------------------------------------------------------------------------
 // Running moments of the two (kinetic_moments.hip: the BAOAB or the GHMC walker with Welford pairs beside position and velocity)
@@ -381,6 +395,5 @@ int kinetic_moments_chain_launch(const KineticMomentsChainReq&, hipStream_t);
 int kinetic_moments_check_geometry(int32_t dim);  // 0, or the refusal (dim outside 1 .. 256)
 // ... on the MLP energy (mlp_wide_kinetic_moments.hip, mlp_wide_ghmc_moments.hip: the same request; the walks of the two MLP entries above with the Welford pairs kept in the caller's planes, updated in place once per counted transition)
 int kinetic_moments_mlp_chain_launch(const KineticMomentsChainReq&, hipStream_t);
-int kinetic_moments_mlp_check_shape(int32_t hidden, int32_t dim);  // 0, or the refusal (hidden width not 64 / 128, dim outside 1 .. 128)
 
 }  // namespace ebm

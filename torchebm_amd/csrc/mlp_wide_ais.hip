@@ -12,18 +12,9 @@ namespace ebm {
 
 int launch_ais_mlp_wide_h128(const widemlp::WideAisArgs& a, hipStream_t st, const char* who);  // mlp_wide_ais_h128.hip
 
-// The refusal that depends on the shape (no launch, no device access): ebm_ais_mlp_chain_f32 calls this in front of its early
-// return for an empty call, so it needs no GPU.
-int ais_mlp_check_shape(int32_t hidden, int32_t dim) {
-  if ((hidden != 64 && hidden != 128) || dim < 1 || dim > 128)
-    return fail(EBM_EDIM, "ebm_ais_mlp_chain_f32: the fused MLP walk supports hidden width 64 or 128 and 1 <= dim <= 128 (got %d, %d)",
-                hidden, dim);
-  return 0;
-}
-
 int ais_mlp_chain_launch(const AisChainReq& q, hipStream_t st) {
   const char* who = "ebm_ais_mlp_chain_f32";
-  if (int r = ais_mlp_check_shape(q.e.n_comp, q.dim)) return r;
+  if (int r = wide_mlp_check_shape(who, q.e.n_comp, q.dim)) return r;
   widemlp::WideAisArgs a{};
   a.x = q.x; a.logw = q.logw; a.n_chains = q.n_chains; a.dim = q.dim; a.n_temps = q.n_temps; a.n_leapfrog = q.n_leapfrog;
   a.beta = q.beta; a.eps = q.eps; a.sigma0 = q.sigma0; a.inv_var0 = q.inv_var0;

@@ -12,18 +12,9 @@ namespace ebm {
 
 int launch_ghmc_mlp_wide_h128(const widemlp::WideGhmcArgs& a, hipStream_t st, const char* who);  // mlp_wide_ghmc_h128.hip
 
-// The refusal that depends on the shape (no launch, no device access): ebm_ghmc_mlp_chain_f32 calls this in front of its early
-// return for an empty call, so it needs no GPU.
-int ghmc_mlp_check_shape(int32_t hidden, int32_t dim) {
-  if ((hidden != 64 && hidden != 128) || dim < 1 || dim > 128)
-    return fail(EBM_EDIM, "ebm_ghmc_mlp_chain_f32: the fused MLP walk supports hidden width 64 or 128 and 1 <= dim <= 128 (got %d, %d)",
-                hidden, dim);
-  return 0;
-}
-
 int ghmc_mlp_chain_launch(const GhmcChainReq& q, hipStream_t st) {
   const char* who = "ebm_ghmc_mlp_chain_f32";
-  if (int r = ghmc_mlp_check_shape(q.e.n_comp, q.dim)) return r;
+  if (int r = wide_mlp_check_shape(who, q.e.n_comp, q.dim)) return r;
   widemlp::WideGhmcArgs a{};
   a.x = q.x; a.v = q.v; a.n_chains = q.n_chains; a.dim = q.dim; a.n_mh = q.n_mh; a.n_leapfrog = q.n_leapfrog;
   a.thin = q.thin; a.n_kept = q.n_kept(); a.draw_v0 = q.draw_v0 ? 1 : 0;

@@ -56,12 +56,7 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_ghmc_chain(WideGhmcArgs a)
   const float eps = a.eps, half_eps = 0.5f * a.eps, c1 = a.c1, c2 = a.c2, beta = a.beta;
   int kept = 0, until_keep = a.thin;
   for (int t = 0; t < a.n_mh; ++t) {  // wave-uniform
-    // Nothing derived from the chain index, the lane's K-half or the key is hoisted out of the transition loop and spilled around
-    // every evaluation (mlp_wide_kinetic_body.h; docs/design/kinetic_mlp.md).
-    int64_t smp = sample;
-    int hq = h;
-    RngKey key = a.key;
-    asm volatile("" : "+v"(smp), "+v"(hq), "+s"(key.k0), "+s"(key.k1));
+    EBM_WIDE_STEP_COPIES_OPAQUE();  // smp, hq, key (mlp_wide_rows.h)
     const Lanes lanes_t{dim, quads, active, hq};  // (the helpers see the opaque K-half)
 
     // ---- O: the partial refresh, two products and a sum, each rounded on its own, a register quad at a time; the refreshed
@@ -75,18 +70,7 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_ghmc_chain(WideGhmcArgs a)
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int c0 = 32 * td + 8 * q + 4 * hq;
-          float z[4];  // (the block of mlp_wide_kinetic_body.h, which says why it is spelled out)
-          if (noise_t) {
-            if (quads && active && c0 + 3 < dim) {
-              const float4 w = *reinterpret_cast<const float4*>(noise_t + smp * dim + c0);
-              z[0] = w.x; z[1] = w.y; z[2] = w.z; z[3] = w.w;
-            } else {
-#pragma unroll
-              for (int j = 0; j < 4; ++j) z[j] = (active && c0 + j < dim) ? noise_t[smp * dim + c0 + j] : 0.0f;
-            }
-          } else {
-            normal_quad(lanes_t, z, key, c0, smp, a.step0 + 1ull + 2ull * (uint64_t)t);
-          }
+          EBM_WIDE_NOISE_QUAD(z, noise_t, lanes_t, a.step0 + 1ull + 2ull * (uint64_t)t);  // (mlp_wide_rows.h)
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             const float vo = c1 * p[td][4 * q + j] + c2 * z[j];

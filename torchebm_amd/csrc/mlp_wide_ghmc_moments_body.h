@@ -63,12 +63,7 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_ghmc_moments_chain(WideGhm
 
   const float eps = a.eps, half_eps = 0.5f * a.eps, c1 = a.c1, c2 = a.c2, beta = a.beta;
   for (int t = 0; t < a.k_steps; ++t) {  // wave-uniform
-    // Nothing derived from the chain index, the lane's K-half or the key is hoisted out of the transition loop and spilled around
-    // every evaluation (mlp_wide_kinetic_body.h; docs/design/kinetic_mlp.md).
-    int64_t smp = sample;
-    int hq = h;
-    RngKey key = a.key;
-    asm volatile("" : "+v"(smp), "+v"(hq), "+s"(key.k0), "+s"(key.k1));
+    EBM_WIDE_STEP_COPIES_OPAQUE();  // smp, hq, key (mlp_wide_rows.h)
     const Lanes lanes_t{dim, quads, active, hq};  // (the helpers see the opaque K-half)
 
     // ---- O: the partial refresh, two products and a sum, each rounded on its own, a register quad at a time; the refreshed
@@ -82,18 +77,7 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_ghmc_moments_chain(WideGhm
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int c0 = 32 * td + 8 * q + 4 * hq;
-          float z[4];  // (the block of mlp_wide_kinetic_body.h, which says why it is spelled out)
-          if (noise_t) {
-            if (quads && active && c0 + 3 < dim) {
-              const float4 w = *reinterpret_cast<const float4*>(noise_t + smp * dim + c0);
-              z[0] = w.x; z[1] = w.y; z[2] = w.z; z[3] = w.w;
-            } else {
-#pragma unroll
-              for (int j = 0; j < 4; ++j) z[j] = (active && c0 + j < dim) ? noise_t[smp * dim + c0 + j] : 0.0f;
-            }
-          } else {
-            normal_quad(lanes_t, z, key, c0, smp, a.step0 + 1ull + 2ull * (uint64_t)t);
-          }
+          EBM_WIDE_NOISE_QUAD(z, noise_t, lanes_t, a.step0 + 1ull + 2ull * (uint64_t)t);  // (mlp_wide_rows.h)
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             const float vo = c1 * p[td][4 * q + j] + c2 * z[j];
@@ -143,10 +127,7 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_ghmc_moments_chain(WideGhm
 
     if (t >= a.burn_in) {  // wave-uniform; a rejected proposal counts the held state again
       const int j = t - a.burn_in;
-      const bool second = j >= a.half_len;
-      const int c = second ? j - a.half_len : j;  // (c + 1 states of this half with this one)
-      const float rc = a.recip[c];                // wave-uniform load
-      const bool first = c == 0;
+      EBM_WIDE_MOMENTS_COUNT(j);  // second, c, rc, first (mlp_wide_rows.h)
       if (!accept) {  // the held position stayed (an opaque pointer again)
         const float* x_plane = a.x;
         asm volatile("" : "+s"(x_plane));
@@ -154,12 +135,10 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_ghmc_moments_chain(WideGhm
       }
       const float e_cnt = accept ? e_last : e_held;
       const int64_t plane = a.n_chains * (int64_t)dim;
-      float* mom_half = a.mom + (second ? 2 * plane : 0);
-      asm volatile("" : "+s"(mom_half));
+      EBM_WIDE_MOMENTS_PLANES(mom_half, a.mom, 2 * plane);
       moments_rows<false>(lanes_t, mom_half, mom_half + plane, smp, xr, rc, first);
       if (a.e_mom) {
-        float* e_half = a.e_mom + (second ? 2 * a.n_chains : 0);
-        asm volatile("" : "+s"(e_half));
+        EBM_WIDE_MOMENTS_PLANES(e_half, a.e_mom, 2 * a.n_chains);
         moments_scalar(lanes_t, e_half, e_half + a.n_chains, smp, e_cnt, rc, first);
       }
       const int64_t kept_row = smp * (2 * (int64_t)a.half_len) + j;

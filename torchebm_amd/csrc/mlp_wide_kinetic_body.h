@@ -55,13 +55,7 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_kinetic_chain(WideKineticA
 
   int kept = 0, until_keep = a.thin;
   for (int i = 0;; ++i) {  // wave-uniform
-    // Nothing derived from the chain index, the lane's K-half or the key is hoisted out of the step loop and spilled around
-    // every evaluation: left invariant, the 64-bit column offsets of the Philox counters (a register pair per element), the
-    // column masks (a scalar pair each) and the round keys are all formed in front of the loop and live through it.
-    int64_t smp = sample;
-    int hq = h;
-    RngKey key = a.key;
-    asm volatile("" : "+v"(smp), "+v"(hq), "+s"(key.k0), "+s"(key.k1));
+    EBM_WIDE_STEP_COPIES_OPAQUE();  // smp, hq, key (mlp_wide_rows.h)
     constexpr bool eval_need_energy = false;
 #include "mlp_wide_plain_eval.inc"
     // The recurrence takes the raw gradient only (no clamp: a NaN stays in its chain) and never the energy.  The energy's chain of
@@ -92,21 +86,7 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_kinetic_chain(WideKineticA
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int c0 = 32 * td + 8 * q + 4 * hq;
-        // The step's noise, injected or drawn.  (Spelled out here and in mlp_wide_ghmc_body.h: as a helper of mlp_wide_rows.h, in
-        // every form tried, the block changed every kernel of this unit -- 62 460 -> ~65 000 lines of disassembly, up to 22 more
-        // VGPRs -- and the register counts of every GHMC kernel.)
-        float z[4];
-        if (noise_i) {
-          if (quads && active && c0 + 3 < dim) {
-            const float4 w = *reinterpret_cast<const float4*>(noise_i + smp * dim + c0);
-            z[0] = w.x; z[1] = w.y; z[2] = w.z; z[3] = w.w;
-          } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) z[j] = (active && c0 + j < dim) ? noise_i[smp * dim + c0 + j] : 0.0f;
-          }
-        } else {
-          normal_quad(lanes, z, key, c0, smp, a.step0 + 1ull + (uint64_t)i);
-        }
+        EBM_WIDE_NOISE_QUAD(z, noise_i, lanes, a.step0 + 1ull + (uint64_t)i);  // (mlp_wide_rows.h)
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           const int r = 4 * q + j;

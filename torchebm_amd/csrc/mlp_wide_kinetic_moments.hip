@@ -2,7 +2,7 @@
 // ebm_kinetic_mlp_chain_f32 and ebm_ghmc_mlp_chain_f32 with the Welford pairs of ebm_kinetic_moments_f32 kept in the caller's
 // planes, in ONE launch (mlp_wide_kinetic_moments_body.h, mlp_wide_ghmc_moments_body.h; docs/design/kinetic_moments_mlp.md).
 // Shapes: hidden width 64 / 128, dim <= 128 -- HT in {2, 4} x DT in {1 .. 4} at wide_mode(HT, DT), as the plain walks.  This unit
-// holds the refusal, the dispatch and the H = 64 BAOAB kernels; mlp_wide_kinetic_moments_h128.hip the H = 128 BAOAB kernels;
+// holds the dispatch and the H = 64 BAOAB kernels; mlp_wide_kinetic_moments_h128.hip the H = 128 BAOAB kernels;
 // mlp_wide_ghmc_moments.hip and mlp_wide_ghmc_moments_h128.hip the GHMC kernels.  Not built: H = 256, MODE 3 / 4, tables, a mass
 // matrix.
 #include "chain_launch.h"
@@ -15,18 +15,9 @@ int launch_kinetic_moments_mlp_wide_h128(const widemlp::WideKineticMomentsArgs& 
 int launch_ghmc_moments_mlp_wide_h64(const widemlp::WideGhmcMomentsArgs& a, hipStream_t st, const char* who);         // mlp_wide_ghmc_moments.hip
 int launch_ghmc_moments_mlp_wide_h128(const widemlp::WideGhmcMomentsArgs& a, hipStream_t st, const char* who);        // mlp_wide_ghmc_moments_h128.hip
 
-// The refusal that depends on the shape (no launch, no device access): ebm_kinetic_moments_mlp_f32 calls this in front of its
-// early return for an empty call, so it needs no GPU.
-int kinetic_moments_mlp_check_shape(int32_t hidden, int32_t dim) {
-  if ((hidden != 64 && hidden != 128) || dim < 1 || dim > 128)
-    return fail(EBM_EDIM, "ebm_kinetic_moments_mlp_f32: the fused MLP walk supports hidden width 64 or 128 and 1 <= dim <= 128 (got %d, %d)",
-                hidden, dim);
-  return 0;
-}
-
 int kinetic_moments_mlp_chain_launch(const KineticMomentsChainReq& q, hipStream_t st) {
   const char* who = "ebm_kinetic_moments_mlp_f32";
-  if (int r = kinetic_moments_mlp_check_shape(q.e.n_comp, q.dim)) return r;
+  if (int r = wide_mlp_check_shape(who, q.e.n_comp, q.dim)) return r;
   if (q.ghmc) {
     widemlp::WideGhmcMomentsArgs a{};
     a.x = q.x; a.v = q.v; a.n_chains = q.n_chains; a.dim = q.dim; a.k_steps = q.k_steps; a.burn_in = q.burn_in;

@@ -1,7 +1,7 @@
 // Running moments of the Euler-Maruyama walk on the wide MLP energy (ebm_chain_moments_mlp_f32): the update of
 // ebm_langevin_chain_f32 without clamp with the Welford pairs of ebm_chain_moments_f32 kept in the caller's planes, in ONE launch
 // (mlp_wide_langevin_moments_body.h; docs/design/langevin_moments_mlp.md).  Shapes: hidden width 64 / 128, dim <= 128 -- HT in
-// {2, 4} x DT in {1 .. 4} at wide_mode(HT, DT), as the other walks.  This unit holds the refusal, the dispatch and the H = 64
+// {2, 4} x DT in {1 .. 4} at wide_mode(HT, DT), as the other walks.  This unit holds the dispatch and the H = 64
 // kernels; mlp_wide_langevin_moments_h128.hip the H = 128 kernels.  Not built: H = 256, MODE 3 / 4, tables, a clamp.
 #include "chain_launch.h"
 #include "mlp_wide_langevin_moments_body.h"
@@ -10,18 +10,9 @@ namespace ebm {
 
 int launch_langevin_moments_mlp_wide_h128(const widemlp::WideLangevinMomentsArgs& a, hipStream_t st, const char* who);  // mlp_wide_langevin_moments_h128.hip
 
-// The refusal that depends on the shape (no launch, no device access): ebm_chain_moments_mlp_f32 calls this in front of its
-// early return for an empty call, so it needs no GPU.
-int langevin_moments_mlp_check_shape(int32_t hidden, int32_t dim) {
-  if ((hidden != 64 && hidden != 128) || dim < 1 || dim > 128)
-    return fail(EBM_EDIM, "ebm_chain_moments_mlp_f32: the fused MLP walk supports hidden width 64 or 128 and 1 <= dim <= 128 (got %d, %d)",
-                hidden, dim);
-  return 0;
-}
-
 int langevin_moments_mlp_chain_launch(const LangevinMomentsChainReq& q, hipStream_t st) {
   const char* who = "ebm_chain_moments_mlp_f32";
-  if (int r = langevin_moments_mlp_check_shape(q.e.n_comp, q.dim)) return r;
+  if (int r = wide_mlp_check_shape(who, q.e.n_comp, q.dim)) return r;
   widemlp::WideLangevinMomentsArgs a{};
   a.x = q.x; a.n_chains = q.n_chains; a.dim = q.dim; a.k_steps = q.k_steps; a.burn_in = q.burn_in;
   a.half_len = q.half_len();

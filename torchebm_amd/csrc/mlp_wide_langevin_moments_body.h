@@ -54,12 +54,7 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_langevin_moments_chain(Wid
 
   for (int i = 0;; ++i) {  // wave-uniform
     if (i == a.k_steps && !want_energy) break;  // nothing is evaluated behind the last step
-    // Nothing derived from the chain index, the lane's K-half or the key is hoisted out of the step loop and spilled around
-    // every evaluation (mlp_wide_kinetic_body.h; docs/design/kinetic_mlp.md).
-    int64_t smp = sample;
-    int hq = h;
-    RngKey key = a.key;
-    asm volatile("" : "+v"(smp), "+v"(hq), "+s"(key.k0), "+s"(key.k1));
+    EBM_WIDE_STEP_COPIES_OPAQUE();  // smp, hq, key (mlp_wide_rows.h)
     constexpr bool eval_need_energy = true;
 #include "mlp_wide_plain_eval.inc"
     // the raw gradient (no clamp: a NaN stays in its chain) and, for i >= 1, the unclamped energy of the state behind step i - 1
@@ -67,13 +62,10 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_langevin_moments_chain(Wid
       const int j = i - 1 - a.burn_in;
       const int64_t kept_row = smp * (2 * (int64_t)a.half_len) + j;
       if (a.e_mom) {
-        const bool second = j >= a.half_len;
-        const int c = second ? j - a.half_len : j;  // (c + 1 states of this half with this one)
-        const float rc = a.recip[c];                // wave-uniform load
+        EBM_WIDE_MOMENTS_COUNT(j);  // second, c, rc, first (mlp_wide_rows.h)
         const Lanes lanes_i{dim, quads, active, hq};  // (the helpers see the opaque K-half)
-        float* e_half = a.e_mom + (second ? 2 * a.n_chains : 0);
-        asm volatile("" : "+s"(e_half));
-        moments_scalar(lanes_i, e_half, e_half + a.n_chains, smp, energy, rc, c == 0);
+        EBM_WIDE_MOMENTS_PLANES(e_half, a.e_mom, 2 * a.n_chains);
+        moments_scalar(lanes_i, e_half, e_half + a.n_chains, smp, energy, rc, first);
       }
       if (a.e_traj && active && hq == 0) a.e_traj[kept_row] = energy;
     }
@@ -86,39 +78,16 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_langevin_moments_chain(Wid
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int c0 = 32 * td + 8 * q + 4 * hq;
-        float z[4];  // (the block of mlp_wide_kinetic_body.h, which says why it is spelled out)
-        if (noise_i) {
-          if (quads && active && c0 + 3 < dim) {
-            const float4 w = *reinterpret_cast<const float4*>(noise_i + smp * dim + c0);
-            z[0] = w.x; z[1] = w.y; z[2] = w.z; z[3] = w.w;
-          } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) z[j] = (active && c0 + j < dim) ? noise_i[smp * dim + c0 + j] : 0.0f;
-          }
-        } else {
-          normal_quad(lanes, z, key, c0, smp, a.step0 + (uint64_t)i);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int r = 4 * q + j;
-          const float x1 = xr[td][r] - eta * g[td][r];
-          const float dw = z[j] * sqrt_eta;
-          const float nv = x1 + noise_coef * dw;
-          xr[td][r] = (c0 + j < dim) ? nv : 0.0f;
-        }
+        EBM_WIDE_NOISE_QUAD(z, noise_i, lanes, a.step0 + (uint64_t)i);  // (mlp_wide_rows.h)
+        EBM_WIDE_EULER_MARUYAMA_QUAD();
       }
     if (i >= a.burn_in) {  // wave-uniform: step i is counted, the state behind it
       const int j = i - a.burn_in;
-      const bool second = j >= a.half_len;
-      const int c = second ? j - a.half_len : j;
-      const float rc = a.recip[c];
+      EBM_WIDE_MOMENTS_COUNT(j);
       const Lanes lanes_i{dim, quads, active, hq};
       const int64_t plane = a.n_chains * (int64_t)dim;
-      // (the planes through opaque copies of their pointers: nothing of them is forwarded from one counted step to the next
-      // in registers)
-      float* mom_half = a.mom + (second ? 2 * plane : 0);
-      asm volatile("" : "+s"(mom_half));
-      moments_rows<false>(lanes_i, mom_half, mom_half + plane, smp, xr, rc, c == 0);
+      EBM_WIDE_MOMENTS_PLANES(mom_half, a.mom, 2 * plane);
+      moments_rows<false>(lanes_i, mom_half, mom_half + plane, smp, xr, rc, first);
       if (a.traj && active) store_rows(lanes_i, a.traj, smp * (2 * (int64_t)a.half_len) + j, xr);
     }
   }

@@ -1,10 +1,11 @@
 // What the walks on the wide MLP energy share besides the evaluation (docs/design/mlp_wide.md, "Shared code of the walks"):
 // the lane-layout helpers -- rows of a [.., dim] matrix to and from the 32x32 C/D layout, the normal field a register quad at a
-// time, the plain kinetic energy --, the macros that go with the plain evaluation (mlp_wide_plain_eval.inc) and the host launcher.
-// Users: mlp_wide_hmc_body.h, mlp_wide_ais_body.h, mlp_wide_kinetic_body.h, mlp_wide_ghmc_body.h and the two running-moments
-// bodies (mlp_wide_kinetic_moments_body.h, mlp_wide_ghmc_moments_body.h: moments_rows, moments_scalar); the leapfrog state machine
-// of the AIS and GHMC walks is text of its own, mlp_wide_leapfrog.inc.  How a helper is spelled and called decides registers
-// and schedule of kernels at the register limit; where a body keeps a block in its own words, it says what the helper cost.
+// time, the plain kinetic energy --, the blocks of the step loops that are shared as text (macros), the running moments, the
+// macros that go with the plain evaluation (mlp_wide_plain_eval.inc) and the host launcher.  Users: the bodies of the nine walks,
+// mlp_wide_{hmc,ais,kinetic,ghmc,tempering,kinetic_moments,ghmc_moments,langevin_moments,tempering_langevin}_body.h; the leapfrog
+// state machine of the AIS, GHMC and tempered-HMC walks is text of its own, mlp_wide_leapfrog.inc.  How a helper is spelled and
+// called decides registers and schedule of kernels at the register limit; where a body keeps a block in its own words, it says
+// what the helper cost.
 #pragma once
 #include <type_traits>
 #include "mlp_wide_body.h"
@@ -17,7 +18,7 @@ namespace widemlp {
 // four kernels are the hand-inlined lambdas' instruction for instruction; with dim / quads / active copied into the struct three
 // of them take 8, 3 and 2 more VGPRs; with the K-half passed to the helpers by value three of them come out with another
 // schedule (62 460 -> 62 869 lines of disassembly).  A walk that keeps an opaque copy of its K-half inside its step loop
-// (mlp_wide_kinetic_body.h says why) binds a second Lanes to that copy there.
+// (EBM_WIDE_STEP_COPIES_OPAQUE below) binds a second Lanes to that copy there.
 struct Lanes {
   const int& dim;
   const bool& quads;   // a register quad r = 4q .. 4q+3 is four consecutive, 16-byte aligned columns
@@ -86,6 +87,87 @@ __device__ __forceinline__ void normal_quad(const Lanes& L, float (&z)[4], RngKe
 #pragma unroll
   for (int i = 0; i < 4; ++i) z[i] = (c0 + i < L.dim) ? z[i] : 0.0f;
 }
+
+// ---- Blocks of the walks' step loops, shared as TEXT.  The walk kernels sit at the register limit, and a block of theirs put
+// into a function -- __forceinline__, a lambda, a by-value return, a callable -- comes out as other code: the noise quad below
+// changed every BAOAB kernel (62 460 -> ~65 000 lines of disassembly, up to 22 more VGPRs) and the register counts of every GHMC
+// kernel, the swap decision both tempered units.  As a macro the block is the tokens the body used to spell out, and every kernel
+// is the instructions it was (docs/design/mlp_wide.md, "Shared code of the walks").  The macros read the names of the set-up
+// and of the loop they stand in (named at each) and declare the ones they say.
+
+// In front of every evaluation of a step loop: opaque per-iteration copies smp / hq / key of the chain index, the lane's K-half
+// and the key.  Nothing derived from them is then hoisted out of the loop and spilled around every evaluation: left invariant,
+// the 64-bit column offsets of the Philox counters (a register pair per element), the column masks (a scalar pair each) and the
+// round keys are all formed in front of the loop and live through it (docs/design/kinetic_mlp.md).  The helpers above see the
+// opaque K-half through a second Lanes bound to hq.
+#define EBM_WIDE_STEP_COPIES_OPAQUE() \
+  int64_t smp = sample;               \
+  int hq = h;                         \
+  RngKey key = a.key;                 \
+  asm volatile("" : "+v"(smp), "+v"(hq), "+s"(key.k0), "+s"(key.k1))
+
+// float Z[4]: the step's noise of the register quad at column c0, injected (NOISE, the step's [n_chains, dim] plane, or null)
+// or drawn at Philox step STEP through the Lanes L.  Reads quads, active, dim, c0, smp, key.
+#define EBM_WIDE_NOISE_QUAD(Z, NOISE, L, STEP)                                                                         \
+  float Z[4];                                                                                                          \
+  if (NOISE) {                                                                                                         \
+    if (quads && active && c0 + 3 < dim) {                                                                             \
+      const float4 w = *reinterpret_cast<const float4*>(NOISE + smp * dim + c0);                                       \
+      Z[0] = w.x; Z[1] = w.y; Z[2] = w.z; Z[3] = w.w;                                                                  \
+    } else {                                                                                                           \
+      _Pragma("unroll") for (int j = 0; j < 4; ++j) Z[j] = (active && c0 + j < dim) ? NOISE[smp * dim + c0 + j] : 0.0f; \
+    }                                                                                                                  \
+  } else {                                                                                                             \
+    normal_quad(L, Z, key, c0, smp, STEP);                                                                             \
+  }
+
+// The Euler-Maruyama update of the quad (td, q) at c0:  x1 = x - eta g;  dw = z sqrt_eta;  x' = x1 + noise_coef dw, every
+// operation rounded on its own.  Reads td, q, c0, xr, g, z, eta, sqrt_eta, noise_coef, dim.
+#define EBM_WIDE_EULER_MARUYAMA_QUAD()                \
+  _Pragma("unroll") for (int j = 0; j < 4; ++j) {     \
+    const int r = 4 * q + j;                          \
+    const float x1 = xr[td][r] - eta * g[td][r];      \
+    const float dw = z[j] * sqrt_eta;                 \
+    const float nv = x1 + noise_coef * dw;            \
+    xr[td][r] = (c0 + j < dim) ? nv : 0.0f;           \
+  }
+
+// The swap event of the tempered walks, decided: slot s pairs with s + 1 when s has the event's parity, with s - 1 otherwise
+// (the ends may be unpaired); both partners -- neighbouring lanes of one K-half -- form the same delta from the same two energies
+// and read the same uniform, the lower slot's: U, the caller's [n_events, n_chains] or null, else the draw at Philox step STEP.
+// E_NOW is the energy of the state the lane's slot holds.  Declares parity, lower, lo, paired, partner and swap; reads slot,
+// event, R, lane, active, smp, key, a.beta, a.n_chains.
+#define EBM_WIDE_SWAP_DECISION(E_NOW, U, STEP)                                                                          \
+  const int parity = event & 1;                                                                                        \
+  const bool lower = ((slot - parity) & 1) == 0;                                                                       \
+  const int lo = lower ? slot : slot - 1;                                                                              \
+  const bool paired = active && lo >= parity && lo + 1 < R;                                                            \
+  const int partner = paired ? (lower ? lane + 1 : lane - 1) : lane;                                                   \
+  const float e_other = __shfl(E_NOW, partner);                                                                        \
+  bool swap = false;                                                                                                   \
+  if (paired) {                                                                                                        \
+    const float e_lo = lower ? E_NOW : e_other, e_hi = lower ? e_other : E_NOW;                                        \
+    const float delta = (a.beta[lo] - a.beta[lo + 1]) * (e_lo - e_hi);                                                 \
+    const int64_t urow = lower ? smp : smp - 1;                                                                        \
+    float us;                                                                                                          \
+    if (U) us = U[(int64_t)event * a.n_chains + urow];                                                                 \
+    else us = u01_half_open(pick(philox_at(key, (uint64_t)urow >> 2, STEP), (int)(urow & 3)));                         \
+    swap = delta == delta && us < expf(fminf(delta, 0.0f));                                                            \
+  }
+
+// The Welford bookkeeping of the counted state J (0-based behind the burn-in) of a running-moments walk: which half it falls in,
+// c (c + 1 states of this half with this one), rc = float32(1 / (c + 1)) by a wave-uniform load, and first: the pair starts from
+// zero.  Reads a.half_len, a.recip.
+#define EBM_WIDE_MOMENTS_COUNT(J)               \
+  const bool second = (J) >= a.half_len;        \
+  const int c = second ? (J) - a.half_len : (J); \
+  const float rc = a.recip[c];                  \
+  const bool first = c == 0
+// ... and float* NAME, the half's planes of BASE (the second half lies STRIDE floats behind the first), through an opaque copy
+// of the pointer: nothing of a plane is forwarded from one counted step to the next in registers
+#define EBM_WIDE_MOMENTS_PLANES(NAME, BASE, STRIDE) \
+  float* NAME = BASE + (second ? STRIDE : 0);       \
+  asm volatile("" : "+s"(NAME))
 
 // The running moments of a walk kept in the CALLER's planes (mlp_wide_kinetic_moments_body.h, mlp_wide_ghmc_moments_body.h;
 // docs/design/kinetic_moments_mlp.md): one in-place update of a row, a register quad at a time, so nothing of a plane lives in

@@ -14,21 +14,9 @@ namespace ebm {
 
 int launch_tempering_mlp_wide_h128(const widemlp::WideTemperArgs& a, hipStream_t st, const char* who);  // mlp_wide_tempering_h128.hip
 
-// The refusal that depends on the shape (no launch, no device access): ebm_tempering_hmc_mlp_chain_f32 calls this in front of its
-// early return for an empty call, so it needs no GPU.
-int tempering_hmc_mlp_check_shape(int32_t hidden, int32_t dim, int32_t n_replicas) {
-  const bool ladder_ok = n_replicas == 2 || n_replicas == 4 || n_replicas == 8 || n_replicas == 16 || n_replicas == 32;
-  if ((hidden != 64 && hidden != 128) || dim < 1 || dim > 128 || !ladder_ok)
-    return fail(EBM_EDIM,
-                "ebm_tempering_hmc_mlp_chain_f32: the fused MLP ladder supports hidden width 64 or 128, 1 <= dim <= 128 and "
-                "2, 4, 8, 16 or 32 replicas (got %d, %d, %d)",
-                hidden, dim, n_replicas);
-  return 0;
-}
-
 int tempering_hmc_mlp_chain_launch(const TemperingHmcChainReq& q, hipStream_t st) {
   const char* who = "ebm_tempering_hmc_mlp_chain_f32";
-  if (int r = tempering_hmc_mlp_check_shape(q.e.n_comp, q.dim, q.n_replicas)) return r;
+  if (int r = wide_mlp_check_ladder_shape(who, q.e.n_comp, q.dim, q.n_replicas)) return r;
   widemlp::WideTemperArgs a{};
   a.x = q.x; a.n_chains = q.n_ladders * (int64_t)q.n_replicas; a.R = q.n_replicas; a.dim = q.dim; a.n_mh = q.n_mh;
   a.n_leapfrog = q.n_leapfrog; a.swap_every = q.swap_every; a.thin = q.thin; a.n_kept = q.n_kept();

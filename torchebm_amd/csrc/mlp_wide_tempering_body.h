@@ -55,12 +55,7 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_tempering_chain(WideTemper
   uint32_t n_accepted = 0u, n_swapped = 0u;  // of this lane's slot; of the pair whose lower slot it is (counted where h == 0)
   int kept = 0, until_keep = a.thin, until_swap = a.swap_every, event = 0;
   for (int t = 0; t < a.n_mh; ++t) {  // wave-uniform
-    // Nothing derived from the chain index, the lane's K-half or the key is hoisted out of the transition loop and spilled around
-    // every evaluation (mlp_wide_kinetic_body.h; docs/design/kinetic_mlp.md): the slot and its constants are formed here.
-    int64_t smp = sample;
-    int hq = h;
-    RngKey key = a.key;
-    asm volatile("" : "+v"(smp), "+v"(hq), "+s"(key.k0), "+s"(key.k1));
+    EBM_WIDE_STEP_COPIES_OPAQUE();  // smp, hq, key (mlp_wide_rows.h): the slot and its constants are formed here.
     const Lanes lanes_t{dim, quads, active, hq};  // (the helpers see the opaque K-half)
     const int slot = (int)smp & (R - 1);
     const float eps = a.eps[slot], half_eps = 0.5f * eps, sqrt_temp = a.sqrt_temp[slot], beta = a.beta[slot];
@@ -74,18 +69,7 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_tempering_chain(WideTemper
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int c0 = 32 * td + 8 * q + 4 * hq;
-          float z[4];  // (the block of mlp_wide_kinetic_body.h, which says why it is spelled out)
-          if (noise_t) {
-            if (quads && active && c0 + 3 < dim) {
-              const float4 w = *reinterpret_cast<const float4*>(noise_t + smp * dim + c0);
-              z[0] = w.x; z[1] = w.y; z[2] = w.z; z[3] = w.w;
-            } else {
-#pragma unroll
-              for (int j = 0; j < 4; ++j) z[j] = (active && c0 + j < dim) ? noise_t[smp * dim + c0 + j] : 0.0f;
-            }
-          } else {
-            normal_quad(lanes_t, z, key, c0, smp, a.step0 + 3ull * (uint64_t)t);
-          }
+          EBM_WIDE_NOISE_QUAD(z, noise_t, lanes_t, a.step0 + 3ull * (uint64_t)t);  // (mlp_wide_rows.h)
 #pragma unroll
           for (int j = 0; j < 4; ++j) p[td][4 * q + j] = (c0 + j < dim) ? sqrt_temp * z[j] : 0.0f;
         }
@@ -128,26 +112,10 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_tempering_chain(WideTemper
 
     if (event_now) {
       until_swap = a.swap_every;
-      // ---- the swap event: slot s pairs with s + 1 when s has the event's parity, with s - 1 otherwise (the ends may be
-      // unpaired); both partners -- neighbouring lanes of one K-half -- form the same delta from the same two energies and read
-      // the same uniform, the lower slot's
+      // ---- the swap event (EBM_WIDE_SWAP_DECISION, mlp_wide_rows.h: lower, partner, swap), on the energy of the state the slot
+      // now holds
       const float e_now = accept ? e_last : e0;
-      const int parity = event & 1;
-      const bool lower = ((slot - parity) & 1) == 0;
-      const int lo = lower ? slot : slot - 1;
-      const bool paired = active && lo >= parity && lo + 1 < R;
-      const int partner = paired ? (lower ? lane + 1 : lane - 1) : lane;
-      const float e_other = __shfl(e_now, partner);
-      bool swap = false;
-      if (paired) {
-        const float e_lo = lower ? e_now : e_other, e_hi = lower ? e_other : e_now;
-        const float delta = (a.beta[lo] - a.beta[lo + 1]) * (e_lo - e_hi);
-        const int64_t urow = lower ? smp : smp - 1;
-        float us;
-        if (a.u_swap) us = a.u_swap[(int64_t)event * a.n_chains + urow];
-        else us = u01_half_open(pick(philox_at(key, (uint64_t)urow >> 2, a.step0 + 3ull * (uint64_t)t + 2ull), (int)(urow & 3)));
-        swap = delta == delta && us < expf(fminf(delta, 0.0f));
-      }
+      EBM_WIDE_SWAP_DECISION(e_now, a.u_swap, a.step0 + 3ull * (uint64_t)t + 2ull);
       if (__any(swap)) {  // wave-uniform: every lane takes part in the cross-lane reads
 #pragma unroll
         for (int td = 0; td < DT; ++td)

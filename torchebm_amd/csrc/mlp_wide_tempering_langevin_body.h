@@ -74,12 +74,7 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_tempering_langevin_chain(W
         store_rows(lanes, a.traj, (sample >> log2_r) * (int64_t)a.n_kept + kept, xr);
       break;
     }
-    // Nothing derived from the chain index, the lane's K-half or the key is hoisted out of the step loop and spilled around
-    // every evaluation (mlp_wide_kinetic_body.h; docs/design/kinetic_mlp.md): the slot and its constant are formed here.
-    int64_t smp = sample;
-    int hq = h;
-    RngKey key = a.key;
-    asm volatile("" : "+v"(smp), "+v"(hq), "+s"(key.k0), "+s"(key.k1));
+    EBM_WIDE_STEP_COPIES_OPAQUE();  // smp, hq, key (mlp_wide_rows.h): the slot and its constant are formed here.
     const Lanes lanes_i{dim, quads, active, hq};  // (the helpers see the opaque K-half)
     const int slot = (int)smp & (R - 1);
     constexpr bool eval_need_energy = true;
@@ -87,25 +82,8 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_tempering_langevin_chain(W
     // the raw gradient and the unclamped energy of the state behind step i - 1 (no clamp: a NaN stays in its ladder)
 
     if (event_now) {
-      // ---- the swap event behind step i - 1: slot s pairs with s + 1 when s has the event's parity, with s - 1 otherwise (the
-      // ends may be unpaired); both partners -- neighbouring lanes of one K-half -- form the same delta from the same two energies
-      // and read the same uniform, the lower slot's
-      const int parity = event & 1;
-      const bool lower = ((slot - parity) & 1) == 0;
-      const int lo = lower ? slot : slot - 1;
-      const bool paired = active && lo >= parity && lo + 1 < R;
-      const int partner = paired ? (lower ? lane + 1 : lane - 1) : lane;
-      const float e_other = __shfl(energy, partner);
-      bool swap = false;
-      if (paired) {
-        const float e_lo = lower ? energy : e_other, e_hi = lower ? e_other : energy;
-        const float delta = (a.beta[lo] - a.beta[lo + 1]) * (e_lo - e_hi);
-        const int64_t urow = lower ? smp : smp - 1;
-        float us;
-        if (a.u) us = a.u[(int64_t)event * a.n_chains + urow];
-        else us = u01_half_open(pick(philox_at(key, (uint64_t)urow >> 2, a.step0 + 2ull * (uint64_t)i - 1ull), (int)(urow & 3)));
-        swap = delta == delta && us < expf(fminf(delta, 0.0f));
-      }
+      // ---- the swap event behind step i - 1 (EBM_WIDE_SWAP_DECISION, mlp_wide_rows.h: lower, partner, swap)
+      EBM_WIDE_SWAP_DECISION(energy, a.u, a.step0 + 2ull * (uint64_t)i - 1ull);
       if (__any(swap)) {  // wave-uniform: every lane takes part in the cross-lane reads
 #pragma unroll
         for (int td = 0; td < DT; ++td)
@@ -136,30 +114,14 @@ __global__ __launch_bounds__(kBlock, 1) void mlp_wide_tempering_langevin_chain(W
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int c0 = 32 * td + 8 * q + 4 * hq;
-        float z[4];  // (the block of mlp_wide_kinetic_body.h, which says why it is spelled out)
-        if (noise_i) {
-          if (quads && active && c0 + 3 < dim) {
-            const float4 w = *reinterpret_cast<const float4*>(noise_i + smp * dim + c0);
-            z[0] = w.x; z[1] = w.y; z[2] = w.z; z[3] = w.w;
-          } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) z[j] = (active && c0 + j < dim) ? noise_i[smp * dim + c0 + j] : 0.0f;
-          }
-        } else {
-          normal_quad(lanes_i, z, key, c0, smp, a.step0 + 2ull * (uint64_t)i);
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const int r = 4 * q + j;
-          const float x1 = xr[td][r] - eta * g[td][r];
-          const float dw = z[j] * sqrt_eta;
-          const float nv = x1 + noise_coef * dw;
-          xr[td][r] = (c0 + j < dim) ? nv : 0.0f;
-        }
+        EBM_WIDE_NOISE_QUAD(z, noise_i, lanes_i, a.step0 + 2ull * (uint64_t)i);  // (mlp_wide_rows.h)
+        EBM_WIDE_EULER_MARUYAMA_QUAD();
       }
   }
   if (active) store_rows(lanes, a.x, sample, xr);
 
+  // (the flush is spelled out here and in mlp_wide_tempering_body.h: one text for the tables of 2 R and 3 R words changed this
+  // kernel, docs/design/mlp_wide.md)
   if (a.swap_counts) {  // wave-uniform; every wave of the workgroup ran the same k_steps steps
     // by slot across the wave: the lanes m, m + R, m + 2 R, .. of the K-half 0 hold one slot (the K-half 1 counted nothing)
     for (int d = R; d < 32; d <<= 1) n_swapped += __shfl_xor(n_swapped, d);

@@ -1,11 +1,12 @@
 """Host machinery the chain samplers share: the outputs and kept-state statistics of a call, the step route's HIP-graph
 replay, the device table of a scheduled step size, and the two drivers of a fused call with diagnostics (in-kernel
-records + merge, or one launch per kept step + passes over the state).  The plain fused call needs none of it."""
+records + merge, or one launch per kept step + passes over the state).  The plain fused call needs none of it.  And the one
+rule every sampler's routing asks: which ``MLPEnergy`` shapes the fused walks on the wide MLP energy take."""
 
 from __future__ import annotations
 
 import threading
-from typing import Dict
+from typing import Dict, Optional
 
 import torch
 
@@ -14,6 +15,20 @@ from ..core.module import ForwardProbe, graph_blind_spots, warn_once
 
 _RECORD_SCRATCH_KEEP_BYTES = 16 << 20
 _CAPTURE_LOCK = threading.Lock()  # serialises graph capture: it toggles the process-wide cyclic GC
+
+#: the shapes of the fused walks on the wide MLP energy (``wide_mlp_check_shape`` / ``wide_mlp_check_ladder_shape`` of
+#: csrc/chain_launch.h refuse the rest): the hidden widths, the widest row -- four state tiles of 32 columns -- and the ladder
+#: lengths of the two tempered walks, whole ladders per 32-row wave
+FUSED_MLP_HIDDEN = (64, 128)
+FUSED_MLP_MAX_DIM = 128
+FUSED_MLP_LADDERS = (2, 4, 8, 16, 32)
+
+
+def fused_mlp_walk_fits(hidden: Optional[int], in_dim: Optional[int], dim: int, n_replicas: Optional[int] = None) -> bool:
+    """Whether a state of ``dim`` columns on an ``MLPEnergy`` of ``hidden`` (its spec's ``n_comp``) and ``in_dim`` -- and, for a
+    tempered walk, a ladder of ``n_replicas`` slots -- fits the fused MLP walks.  Opt-in flags, dtype and device are the caller's."""
+    return bool(hidden in FUSED_MLP_HIDDEN and dim == in_dim and dim <= FUSED_MLP_MAX_DIM
+                and (n_replicas is None or n_replicas in FUSED_MLP_LADDERS))
 
 
 # -------------------------------------------------------------------------------------

@@ -34,6 +34,7 @@ import torch
 from .. import _lib, _rng
 from ..core.energies import BaseModel, FusedSpec, fused_spec_for
 from ..core.module import TorchEBMModule
+from ._chain_host import fused_mlp_walk_fits
 
 
 def ais_betas(n_temperatures: int, schedule: str = "linear", sharpness: float = 4.0) -> torch.Tensor:
@@ -175,8 +176,7 @@ class AnnealedImportanceSampling(TorchEBMModule):
         if spec is None:
             return "eager", None
         if spec.kind == _lib.ENERGY_MLP:
-            if (self.fused_mlp and spec.hmc and spec.n_comp in (64, 128) and dim == getattr(self.model, "in_dim", None)
-                    and dim <= 128):
+            if self.fused_mlp and spec.hmc and fused_mlp_walk_fits(spec.n_comp, getattr(self.model, "in_dim", None), dim):
                 return "fused_mlp", spec
             return "eager", None
         return "fused", spec

@@ -43,10 +43,10 @@ from .. import _lib, _rng
 from ..core.energies import BaseModel, FusedSpec, fused_spec_for
 from ..core.sampler_base import BaseSampler
 from ..core.schedules import BaseScheduler
-from ._chain_host import kept_statistics, new_outputs, record_kept
+from ._chain_host import (FUSED_MLP_MAX_DIM, fused_mlp_walk_fits, kept_statistics, new_outputs,  # noqa: F401
+                          record_kept)  # (FUSED_MLP_MAX_DIM: importable from here as before)
 
 FUSED_MAX_DIM = 256  # one vector per lane (csrc/ghmc.hip)
-FUSED_MLP_MAX_DIM = 128  # four state tiles of 32 columns (csrc/mlp_wide_ghmc.hip)
 
 
 def ghmc_constants(eps: float, n_leapfrog: int, friction: float, temperature: float,
@@ -121,7 +121,7 @@ class GeneralizedHMC(BaseSampler):
             return "eager", None
         if spec.kind == _lib.ENERGY_MLP:
             dim = x.shape[1]
-            if self.fused_mlp and spec.n_comp in (64, 128) and dim == getattr(self.model, "in_dim", None) and dim <= FUSED_MLP_MAX_DIM:
+            if self.fused_mlp and fused_mlp_walk_fits(spec.n_comp, getattr(self.model, "in_dim", None), dim):
                 return "fused_mlp", spec
             return "eager", None
         return "fused", spec

@@ -39,7 +39,7 @@ from .. import _lib, _rng
 from ..core.energies import BaseModel, FusedSpec, fused_spec_for
 from ..core.sampler_base import BaseSampler
 from ..core.schedules import BaseScheduler
-from ._chain_host import kept_statistics, new_outputs, record_kept
+from ._chain_host import fused_mlp_walk_fits, kept_statistics, new_outputs, record_kept
 
 FUSED_MAX_DIM = 256  # one vector per lane (csrc/kinetic.hip)
 
@@ -104,7 +104,7 @@ class UnderdampedLangevin(BaseSampler):
             return "eager", None
         if spec.kind == _lib.ENERGY_MLP:
             dim = x.shape[1]
-            if self.fused_mlp and spec.n_comp in (64, 128) and dim == getattr(self.model, "in_dim", None) and dim <= 128:
+            if self.fused_mlp and fused_mlp_walk_fits(spec.n_comp, getattr(self.model, "in_dim", None), dim):
                 return "fused_mlp", spec
             return "eager", None
         return "fused", spec

@@ -35,6 +35,7 @@ import torch
 
 from .. import _lib, _rng
 from ..core.energies import fused_spec_for
+from ._chain_host import fused_mlp_walk_fits
 
 SAMPLER_LANGEVIN, SAMPLER_HMC = 0, 1
 FUSED_MAX_DIM = 256
@@ -226,7 +227,7 @@ def fused_mlp_moments_eligible(*, opted_in: bool, dtype: torch.dtype, ndim: int,
     (``"fused"`` only for a CUDA fp32 state: the sampler decides that, here as for ``sample()``), the spec's kind and its
     ``n_comp`` (``None`` without a spec); ``in_dim``: the model's."""
     return bool(opted_in and dtype == torch.float32 and ndim == 2 and n > 0 and route == "fused"
-                and spec_kind == _lib.ENERGY_MLP and hidden in (64, 128) and 1 <= dim <= 128 and dim == in_dim and constant
+                and spec_kind == _lib.ENERGY_MLP and dim >= 1 and fused_mlp_walk_fits(hidden, in_dim, dim) and constant
                 and plain_integrator and not autocast and not has_clamp)
 
 

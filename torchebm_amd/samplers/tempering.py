@@ -43,7 +43,8 @@ from .. import _lib, _rng
 from ..core.energies import BaseModel, FusedSpec, fused_spec_for
 from ..core.sampler_base import BaseSampler
 from ..core.schedules import BaseScheduler
-from ._chain_host import kept_statistics, new_outputs, record_kept
+from ._chain_host import (FUSED_MLP_LADDERS, FUSED_MLP_MAX_DIM, fused_mlp_walk_fits, kept_statistics, new_outputs,  # noqa: F401
+                          record_kept)  # (FUSED_MLP_LADDERS, FUSED_MLP_MAX_DIM: importable from here as before)
 
 
 def ladder_coefficients(noise_scale: float, temperatures: Sequence[float]) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -146,8 +147,7 @@ class ReplicaExchangeLangevin(_LadderSampler):
         spec = fused_spec_for(self.model, rows, None)
         if spec is not None and spec.kind == _lib.ENERGY_MLP:
             dim = rows.shape[1]
-            if (self.fused_mlp_ladder and self.n_replicas in FUSED_MLP_LADDERS and spec.n_comp in (64, 128)
-                    and dim == getattr(self.model, "in_dim", None) and dim <= FUSED_MLP_MAX_DIM):
+            if self.fused_mlp_ladder and fused_mlp_walk_fits(spec.n_comp, getattr(self.model, "in_dim", None), dim, self.n_replicas):
                 return "fused_mlp", spec
             return "eager", None
         if spec is None:
@@ -287,12 +287,6 @@ class ReplicaExchangeLangevin(_LadderSampler):
         return state, (traj if want_traj else None), diag
 
 
-#: the ladder lengths of ``ebm_tempering_mlp_chain_f32`` and ``ebm_tempering_hmc_mlp_chain_f32`` (whole ladders per 32-row
-#: wave) and their widest row
-FUSED_MLP_LADDERS = (2, 4, 8, 16, 32)
-FUSED_MLP_MAX_DIM = 128
-
-
 def hmc_ladder_coefficients(temperatures: Sequence[float]) -> Tuple[torch.Tensor, torch.Tensor]:
     """``(sqrt_temp[R], beta[R])`` as fp32: formed in double, rounded once (include/ebm_hip.h)."""
     t = torch.tensor([float(v) for v in temperatures], dtype=torch.float64)
@@ -386,8 +380,7 @@ class ReplicaExchangeHMC(_LadderSampler):
             return "eager", None
         if spec.kind == _lib.ENERGY_MLP:
             dim = rows.shape[1]
-            if (self.fused_mlp and self.n_replicas in FUSED_MLP_LADDERS and spec.n_comp in (64, 128)
-                    and dim == getattr(self.model, "in_dim", None) and dim <= FUSED_MLP_MAX_DIM):
+            if self.fused_mlp and fused_mlp_walk_fits(spec.n_comp, getattr(self.model, "in_dim", None), dim, self.n_replicas):
                 return "fused_mlp", spec
             return "eager", None
         if self.n_replicas > 64 or self.n_replicas * lanes_per_row(rows.shape[1]) > 256:
