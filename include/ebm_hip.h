@@ -699,12 +699,49 @@ EBM_API int ebm_chain_moments_mlp_f32(const ebm_energy_t* energy, float* x, int6
  * after step s whenever (s + 1) % thin == 0.  Slots of a lane that hold no column never reach memory.
  *
  * Limits: every analytic energy except EBM_ENERGY_MLP (EBM_EKIND); 1 <= dim <= 256, one vector per lane (EBM_EDIM, in front
- * of any device access); constants only: no clamp, no tables, no mass matrix, no diagnostics records; 64-bit row indices.
+ * of any device access); constants only: no clamp, no tables, unit mass (a scalar or diagonal mass:
+ * ebm_kinetic_chain_mass_f32 below; no dense mass), no diagnostics records; 64-bit row indices.
  * EBM_EINVAL with no buffer touched: a NULL energy, x or v; k_steps < 1; thin < 1; h, gamma or temperature not positive.
  */
 EBM_API int ebm_kinetic_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim,
                                   int32_t k_steps, double h, double gamma, double temperature, int32_t draw_v0, int32_t thin,
                                   float* traj, const float* noise, uint64_t seed, uint64_t offset, void* stream);
+
+/*
+ * The two velocity-carrying samplers with a scalar or diagonal mass: ebm_kinetic_chain_mass_f32 (here) and
+ * ebm_ghmc_chain_mass_f32 (behind ebm_ghmc_chain_f32) take the parameter lists of ebm_kinetic_chain_f32 / ebm_ghmc_chain_f32
+ * with `int32_t mass_kind, double mass_scalar, const float* mass_diag` directly behind `temperature`, each in ONE launch
+ * (additions to ABI 9: nothing else moved).  The rules both share:
+ *
+ * Mass forms and clamps: those of ebm_hmc_chain_f32.  EBM_MASS_SCALAR: m_raw = (float)m, m_sqrt = (float)sqrt(m), m_safe =
+ * (float)max(m, 1e-10), formed in double and rounded once.  EBM_MASS_DIAG: mass_diag is a device float[dim]; per element m_raw
+ * = m, m_sqrt = sqrtf(m) (correctly rounded), m_safe = (m < 1e-10) ? 1e-10 : m.  The entries are not inspected.  A slot of a
+ * lane that holds no column of the diagonal gets mass 1; x and p stay 0 there.
+ *
+ * Carried plane: the MOMENTUM p with law N(0, T m), the convention of ebm_hmc_chain_f32.  `v` in the parameter list is that
+ * plane, in and out.  draw_v0 != 0: p = (sqrt_temp * m_sqrt) * z0, z0 the normal field at step offset.
+ *
+ * Unchanged from the unit-mass entries: the constants formed in double, the Philox coordinates and the steps a call owns,
+ * draw_v0, thin / traj, the injected noise / u, the outputs, "two calls equal one", 1 <= dim <= 256 (EBM_EDIM), the refusal
+ * of EBM_ENERGY_MLP (EBM_EKIND) and every EBM_EINVAL.  More EBM_EINVAL, in front of any device access and of the early
+ * return for n_chains == 0, no buffer touched: mass_kind == EBM_MASS_NONE or unknown (callers use the unit-mass entry);
+ * EBM_MASS_DIAG with a NULL mass_diag; EBM_MASS_SCALAR with a mass_scalar that is not positive and finite.
+ *
+ * BAOAB with a mass.  a_j = hh / m_safe_j and s_j = c2 * m_sqrt_j are formed once per coordinate in front of the loop; step
+ * s = 0 .. k_steps - 1, every operation rounded on its own, g the raw unclamped gradient:
+ *     p = p - hh * g            (B)
+ *     x = x + a_j * p           (A)
+ *     p = c1 * p + s_j * z      (O)
+ *     x = x + a_j * p           (A)
+ *     g = dE/dx(x)
+ *     p = p - hh * g            (B)
+ * With every m_j = 1 each line is ebm_kinetic_chain_f32's with an exact factor: the bits are that entry's.  On a quadratic
+ * energy E'' = k the law is the unit-mass one in the coordinate x sqrt(m): var(x) k / T = 1, var(p) / (T m) = 1 - h^2 k / (4 m).
+ */
+EBM_API int ebm_kinetic_chain_mass_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim,
+                                       int32_t k_steps, double h, double gamma, double temperature, int32_t mass_kind,
+                                       double mass_scalar, const float* mass_diag, int32_t draw_v0, int32_t thin, float* traj,
+                                       const float* noise, uint64_t seed, uint64_t offset, void* stream);
 
 /*
  * Underdamped Langevin (BAOAB) on the MLP energy: the walk of ebm_kinetic_chain_f32 above -- the same parameter list, the same
@@ -781,7 +818,8 @@ EBM_API int ebm_kinetic_mlp_chain_f32(const ebm_energy_t* energy, float* x, floa
  * carried energy and force are re-evaluated by the evaluation the last leapfrog step ended on.
  *
  * Limits: every analytic energy except EBM_ENERGY_MLP (EBM_EKIND); 1 <= dim <= 256, one vector per lane (EBM_EDIM, in front
- * of any device access); constants only: no tables, no mass matrix, no diagnostics records; 64-bit row indices.
+ * of any device access); constants only: no tables, unit mass (a scalar or diagonal mass: ebm_ghmc_chain_mass_f32 below; no
+ * dense mass), no diagnostics records; 64-bit row indices.
  * EBM_EINVAL with no buffer touched: a NULL energy, x or v; n_mh < 1, n_leapfrog < 1 or thin < 1; eps, gamma or temperature
  * not positive, or NaN (eps and temperature must be finite).  An empty call (n_chains == 0) returns 0 behind these checks.
  */
@@ -789,6 +827,30 @@ EBM_API int ebm_ghmc_chain_f32(const ebm_energy_t* energy, float* x, float* v, i
                                int32_t n_leapfrog, double eps, double gamma, double temperature, int32_t draw_v0,
                                int32_t thin, float* traj, uint8_t* accept_mask, const float* noise, const float* u,
                                uint64_t seed, uint64_t offset, void* stream);
+
+/*
+ * Generalized HMC with a scalar or diagonal mass (an addition to ABI 9: nothing else moved).  The parameter list, the mass
+ * forms, the carried momentum plane, what stays as in the unit-mass entry and the refusals: the rules stated at
+ * ebm_kinetic_chain_mass_f32.  s_j = c2 * m_sqrt_j and the drift scale eps / m_safe_j are formed once per coordinate in front
+ * of the loop.  Transition t = 0 .. n_mh - 1:
+ *     p  = c1 * p + s_j * z_t                      (O)  two products and a sum, each rounded on its own
+ *     u  = the uniform of this chain
+ *     H0 = clamp(E(x), +-1e10) + K_m(p),  K_m the massed kinetic energy of ebm_hmc_chain_f32: 0.5 sum(p^2 / m_raw) for a
+ *          diagonal mass, (0.5 sum p^2) / m_raw for a scalar one, clamped to [0, 1e10]
+ *     (x', p') = the trajectory of ebm_hmc_chain_f32 with this mass, untouched: safe mode, the drift x += (eps / m_safe) p as
+ *                one FMA, the carried energy and force, the pseudo-transition, merged kicks, the literal fallback
+ *     H1 = clamp(E(x'), +-1e10) + K_m(p')
+ *     d  = clamp(beta * (H0 - H1), +-50);  a = min(1, exp d);  accepted iff u < a (a NaN rejects)
+ *     accepted:  (x, p, E, force) = (x', p', E', force')
+ *     rejected:  x, E and the force stay;  p = -(the p after O)                                  the flip
+ * With every m_j = 1 the bits are ebm_ghmc_chain_f32's.  At gamma = +inf and T = 1, for finite states, this is the transition
+ * of ebm_hmc_chain_f32 with the same mass on the same z and u.
+ */
+EBM_API int ebm_ghmc_chain_mass_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t n_mh,
+                                    int32_t n_leapfrog, double eps, double gamma, double temperature, int32_t mass_kind,
+                                    double mass_scalar, const float* mass_diag, int32_t draw_v0, int32_t thin, float* traj,
+                                    uint8_t* accept_mask, const float* noise, const float* u, uint64_t seed, uint64_t offset,
+                                    void* stream);
 
 /*
  * Generalized HMC on the MLP energy: the sampler of ebm_ghmc_chain_f32 above -- the same parameter list, the same constants

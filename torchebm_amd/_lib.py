@@ -49,8 +49,10 @@ EXPORTS = (
     "ebm_chain_moments_f32",
     "ebm_chain_moments_mlp_f32",
     "ebm_kinetic_chain_f32",
+    "ebm_kinetic_chain_mass_f32",
     "ebm_kinetic_mlp_chain_f32",
     "ebm_ghmc_chain_f32",
+    "ebm_ghmc_chain_mass_f32",
     "ebm_ghmc_mlp_chain_f32",
     "ebm_kinetic_moments_f32",
     "ebm_kinetic_moments_mlp_f32",
@@ -175,11 +177,20 @@ _PROTOTYPES = {
         [_ENERGY_P, _p, _i64, _i32, _i32, _i32, _i32, _f, _f, _f, _i32, _f, _p, _p, _p, _p, _p, _p, _p, _p, _p, _u64, _u64, _p],
     ),
     "ebm_kinetic_chain_f32": (C.c_int, [_ENERGY_P, _p, _p, _i64, _i32, _i32, _d, _d, _d, _i32, _i32, _p, _p, _u64, _u64, _p]),
+    # (... with `int32_t mass_kind, double mass_scalar, const float* mass_diag` behind `temperature`)
+    "ebm_kinetic_chain_mass_f32": (
+        C.c_int,
+        [_ENERGY_P, _p, _p, _i64, _i32, _i32, _d, _d, _d, _i32, _d, _p, _i32, _i32, _p, _p, _u64, _u64, _p],
+    ),
     # (the same parameter list, on the MLP energy)
     "ebm_kinetic_mlp_chain_f32": (C.c_int, [_ENERGY_P, _p, _p, _i64, _i32, _i32, _d, _d, _d, _i32, _i32, _p, _p, _u64, _u64, _p]),
     "ebm_ghmc_chain_f32": (
         C.c_int,
         [_ENERGY_P, _p, _p, _i64, _i32, _i32, _i32, _d, _d, _d, _i32, _i32, _p, _p, _p, _p, _u64, _u64, _p],
+    ),
+    "ebm_ghmc_chain_mass_f32": (  # ... with the same three behind `temperature`
+        C.c_int,
+        [_ENERGY_P, _p, _p, _i64, _i32, _i32, _i32, _d, _d, _d, _i32, _d, _p, _i32, _i32, _p, _p, _p, _p, _u64, _u64, _p],
     ),
     "ebm_ghmc_mlp_chain_f32": (
         C.c_int,

@@ -197,6 +197,25 @@ struct GhmcChainReq {
   int32_t n_kept() const { return n_mh / thin; }
 };
 
+// A scalar or diagonal mass as the massed entries take it (EBM_MASS_SCALAR / EBM_MASS_DIAG; never EBM_MASS_NONE)
+struct ChainMass {
+  int32_t kind;
+  double scalar;      // EBM_MASS_SCALAR: positive and finite
+  const float* diag;  // EBM_MASS_DIAG: device [dim]
+};
+
+// ebm_kinetic_chain_mass_f32: the unit-mass request, whose v is then the momentum plane, and the mass
+struct KineticMassChainReq {
+  KineticChainReq chain;
+  ChainMass mass;
+};
+
+// ebm_ghmc_chain_mass_f32: likewise
+struct GhmcMassChainReq {
+  GhmcChainReq chain;
+  ChainMass mass;
+};
+
 struct KineticMomentsChainReq {
   const ebm_energy_t& e;
   float* x;                // [n_chains, dim], in/out
@@ -237,14 +256,28 @@ inline void fill_langevin(Args& a, const LangevinChainReq& q) {
   a.key = q.key(); a.step0 = q.offset;
 }
 
+// A scalar mass in its three forms: raw (kinetic energy), sqrt (momentum draw), clamped (drift); formed in double, rounded once.
+template <class Args>
+inline void fill_scalar_mass(Args& a, double m) {
+  a.mass_raw = (float)m;
+  a.mass_sqrt = (float)sqrt(m);
+  a.mass_safe = (float)(m < 1e-10 ? 1e-10 : m);
+}
+
+// The mass of the massed kinetic walkers (KineticMassArgs, GhmcMassArgs): the kind, the scalar forms, the diagonal's pointer.
+template <class Args>
+inline void fill_mass(Args& a, const ChainMass& m) {
+  a.mass_kind = m.kind;
+  fill_scalar_mass(a, m.kind == EBM_MASS_SCALAR ? m.scalar : 1.0);
+  a.mass_diag = m.diag;
+}
+
 // The fields the HMC argument structs share (HmcArgs, GaussHmcArgs, WideHmcArgs), the scalar mass in its three forms.
 template <class Args>
 inline void fill_hmc(Args& a, const HmcChainReq& q) {
   a.x = q.x; a.n_chains = q.n_chains; a.dim = q.dim; a.n_mh = q.n_mh; a.n_leapfrog = q.n_leapfrog;
   a.eps = q.eps; a.eps_table = q.eps_table;
-  a.mass_raw = (float)q.mass_scalar;
-  a.mass_sqrt = (float)sqrt(q.mass_scalar);
-  a.mass_safe = (float)(q.mass_scalar < 1e-10 ? 1e-10 : q.mass_scalar);
+  fill_scalar_mass(a, q.mass_scalar);
   a.thin = q.thin; a.n_kept = q.n_kept(); a.traj = q.traj;
   a.accept_mask = q.accept_mask; a.accept_count = q.accept_count; a.p_noise = q.p_noise; a.u = q.u;
   a.key = q.key(); a.step0 = q.offset;
@@ -387,6 +420,12 @@ int ghmc_chain_launch(const GhmcChainReq&, hipStream_t);
 int ghmc_check_geometry(int32_t dim);  // 0, or the refusal (dim > 256)
 // ... on the MLP energy (mlp_wide_ghmc.hip: the same request; 32 chains per wave around the matrix-core evaluation, n_leapfrog + 1 of them per transition)
 int ghmc_mlp_chain_launch(const GhmcChainReq&, hipStream_t);
+
+// ---------------------------------------------------------------------------------
+// The two with a scalar or diagonal mass (kinetic_mass.hip, ghmc_mass.hip: the same walkers, the carried plane the momentum)
+// ---------------------------------------------------------------------------------
+int kinetic_mass_chain_launch(const KineticMassChainReq&, hipStream_t);
+int ghmc_mass_chain_launch(const GhmcMassChainReq&, hipStream_t);
 
 // ---------------------------------------------------------------------------------
 // Running moments of the two (kinetic_moments.hip: the BAOAB or the GHMC walker with Welford pairs beside position and velocity)

@@ -215,6 +215,54 @@ __device__ __forceinline__ bool metropolis_accept(float dH, float uu, bool init,
   return init || (active && (uu < acc_p));
 }
 
+// ---- a scalar or diagonal mass, shared by hmc_chain_body and the massed kinetic walkers (kinetic_mass_kernel.h,
+//      ghmc_mass_kernel.h).  Args carries mass_raw, mass_sqrt, mass_safe (the scalar forms) and mass_diag.
+
+// The mass forms per slot: raw (kinetic energy), sqrt (momentum draw), clamped (drift).  A slot that holds no column gets 1.
+template <class LaneT, class Args>
+__device__ __forceinline__ void mass_forms(const LaneT& L, const Args& a, const bool diag_mass, Slice<LaneT::NV>& m_raw,
+                                           Slice<LaneT::NV>& m_sqrt, Slice<LaneT::NV>& m_safe) {
+  constexpr int NV = LaneT::NV;
+  if (diag_mass) load_param_slice(L, a.mass_diag, 1.0f, m_raw);
+#pragma unroll
+  for (int v = 0; v < NV; ++v)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (diag_mass) {
+        // (sqrtf is correctly rounded here -- hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt; torch's CPU sqrt is NOT:
+        //  it lands on the wrong side of near-halfway cases, differently on different hosts -- tests/test_hmc_audit_gpu.py)
+        m_sqrt.a[v][i] = sqrtf(m_raw.a[v][i]);
+        m_safe.a[v][i] = m_raw.a[v][i] < 1e-10f ? 1e-10f : m_raw.a[v][i];
+      } else {
+        m_raw.a[v][i] = a.mass_raw;
+        m_sqrt.a[v][i] = a.mass_sqrt;
+        m_safe.a[v][i] = a.mass_safe;
+      }
+    }
+}
+
+// K(p) = 0.5 p^T M^-1 p, clamped to [0, 1e10]: per slot p^2 / m of a diagonal mass, the sum / m of a scalar one.
+template <bool HAS_MASS, class LaneT>
+__device__ __forceinline__ float massed_kinetic(const LaneT& L, const Slice<LaneT::NV>& q,
+                                                const Slice<HAS_MASS ? LaneT::NV : 1>& m_raw, bool diag_mass, float mass_raw) {
+  float acc = 0.0f;
+#pragma unroll
+  for (int v = 0; v < LaneT::NV; ++v)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float sq = q.a[v][i] * q.a[v][i];
+      if constexpr (HAS_MASS) {
+        if (diag_mass) sq = sq / m_raw.a[v][i];
+      }
+      acc += L.ok(v, i) ? sq : 0.0f;
+    }
+  float k = 0.5f * group_sum<LaneT::G>(acc);
+  if constexpr (HAS_MASS) {
+    if (!diag_mass) k = k / mass_raw;
+  }
+  return clamp_nanprop(k, 0.0f, 1e10f);
+}
+
 // The AUDIT form of the trajectory (ebm_hmc_chain_audit_f32; tests only): the reference's safe-mode leapfrog step literally
 // (integrators/leapfrog.py:156-185, restated in oracle/hmc.py) -- the force re-evaluated at the top of every step, two separate
 // half kicks, every multiply and add rounded on its own (this file is compiled with -ffp-contract=off and nothing below is an
@@ -294,44 +342,10 @@ __device__ __forceinline__ void hmc_chain_body(const HmcArgs& a) {
   constexpr bool has_mass = MASS != 0;
   const bool diag_mass = has_mass && a.mass_kind == EBM_MASS_DIAG;
   Slice<has_mass ? NV : 1> m_raw, m_sqrt, m_safe;
-  if constexpr (has_mass) {
-    if (diag_mass) load_param_slice(L, a.mass_diag, 1.0f, m_raw);
-#pragma unroll
-    for (int v = 0; v < NV; ++v)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        if (diag_mass) {
-          // (sqrtf is correctly rounded here -- hipcc's default -fhip-fp32-correctly-rounded-divide-sqrt; torch's CPU sqrt is NOT:
-          //  it lands on the wrong side of near-halfway cases, differently on different hosts -- tests/test_hmc_audit_gpu.py)
-          m_sqrt.a[v][i] = sqrtf(m_raw.a[v][i]);
-          m_safe.a[v][i] = m_raw.a[v][i] < 1e-10f ? 1e-10f : m_raw.a[v][i];
-        } else {
-          m_raw.a[v][i] = a.mass_raw;
-          m_sqrt.a[v][i] = a.mass_sqrt;
-          m_safe.a[v][i] = a.mass_safe;
-        }
-      }
-  }
+  if constexpr (has_mass) mass_forms(L, a, diag_mass, m_raw, m_sqrt, m_safe);
 
   // K(p) = 0.5 p^T M^-1 p, clamped to [0, 1e10]  (samplers/hmc.py:136-159, :251-254)
-  auto kinetic = [&](const Slice<NV>& q) -> float {
-    float acc = 0.0f;
-#pragma unroll
-    for (int v = 0; v < NV; ++v)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        float sq = q.a[v][i] * q.a[v][i];
-        if constexpr (has_mass) {
-          if (diag_mass) sq = sq / m_raw.a[v][i];
-        }
-        acc += L.ok(v, i) ? sq : 0.0f;
-      }
-    float k = 0.5f * group_sum<G>(acc);
-    if constexpr (has_mass) {
-      if (!diag_mass) k = k / a.mass_raw;
-    }
-    return clamp_nanprop(k, 0.0f, 1e10f);
-  };
+  auto kinetic = [&](const Slice<NV>& q) -> float { return massed_kinetic<has_mass>(L, q, m_raw, diag_mass, a.mass_raw); };
 
   const int64_t traj_row = L.active ? L.chain * (int64_t)a.n_kept * a.dim : 0;
   int until_keep = a.thin;

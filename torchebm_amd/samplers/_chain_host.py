@@ -32,6 +32,55 @@ def fused_mlp_walk_fits(hidden: Optional[int], in_dim: Optional[int], dim: int, 
 
 
 # -------------------------------------------------------------------------------------
+# the scalar or diagonal mass of the two velocity-carrying samplers (UnderdampedLangevin, GeneralizedHMC)
+# -------------------------------------------------------------------------------------
+def check_mass(mass, device):
+    """The ``mass=`` argument as the sampler keeps it: ``None``, a positive finite float, or a 1-D tensor on ``device``
+    (its entries are not inspected: no host sync)."""
+    import math
+
+    if mass is None:
+        return None
+    if torch.is_tensor(mass):
+        if mass.ndim != 1:
+            raise ValueError(f"mass must be a float or a 1-D tensor, got a tensor of shape {tuple(mass.shape)}")
+        return mass.to(device)
+    if isinstance(mass, bool) or not isinstance(mass, (int, float)):
+        raise ValueError(f"mass must be None, a float or a 1-D tensor, got {type(mass).__name__}")
+    if not (mass > 0 and math.isfinite(mass)):
+        raise ValueError(f"mass must be positive and finite, got {mass}")
+    return float(mass)
+
+
+def mass_row(mass, x: torch.Tensor):
+    """``mass`` as ``p * p / m`` takes it on a state shaped as ``x``: ``None``, the float, or the tensor broadcast along the last
+    width.  Raises ``ValueError`` for a tensor whose length is not that width."""
+    if mass is None or isinstance(mass, float):
+        return mass
+    if mass.numel() != x.shape[-1]:
+        raise ValueError(f"mass tensor must have {x.shape[-1]} entries, got {mass.numel()}")
+    return mass.to(device=x.device, dtype=x.dtype).view((1,) * (x.ndim - 1) + (-1,))
+
+
+def mass_forms(mass, x: torch.Tensor):
+    """``(m_sqrt, m_safe)`` of the contract (include/ebm_hip.h, ebm_kinetic_chain_mass_f32) as tensors of ``x``'s dtype that
+    broadcast against ``x``: ``sqrt(m)`` formed in double and rounded once (correctly rounded, as the kernel's), and
+    ``max(m, 1e-10)``."""
+    if isinstance(mass, float):  # both formed in double, rounded once
+        both = torch.tensor([mass, max(mass, 1e-10)], dtype=torch.float64, device=x.device)
+        return both[0].sqrt().to(x.dtype), both[1].to(x.dtype)
+    m = mass_row(mass, x)
+    return m.to(torch.float64).sqrt().to(x.dtype), torch.where(m < 1e-10, torch.full_like(m, 1e-10), m)
+
+
+def kinetic_temperature(v: torch.Tensor, m=None) -> torch.Tensor:
+    """The mean of ``v^2`` -- with a mass ``m`` (``mass_row``) of ``p^2 / m`` -- over chains and coordinates; NaN for no chain."""
+    if not v.numel():
+        return torch.full((), float("nan"), dtype=v.dtype, device=v.device)
+    return v.square().mean() if m is None else (v.square() / m).mean()
+
+
+# -------------------------------------------------------------------------------------
 # kept states: outputs and their statistics
 # -------------------------------------------------------------------------------------
 def new_outputs(like, shape, n_kept: int, want_traj: bool, want_diag: bool, acceptance: bool = False):

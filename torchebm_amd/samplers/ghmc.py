@@ -29,6 +29,12 @@ Three execution routes, chosen once per ``sample()`` call (``_route``):
            drawing ``randn(n, dim)`` for the start velocities (only when none are passed) and ``randn(n, dim)``, ``rand(n)``
            per transition.
 
+``fused_mass``  a sampler built with ``mass=`` (a float or a per-dimension tensor) under the conditions of ``fused``: ONE launch
+           of ``ebm_ghmc_chain_mass_f32`` (docs/design/mass.md).  The carried plane is then the MOMENTUM ``p ~ N(0, T m)``:
+           ``velocity=`` / ``return_velocity`` carry it; the refresh is ``p = c1 p + c2 sqrt(m) xi``, the kinetic energy
+           ``p^2 / (2 m)`` and the drift ``x += eps p / m``, as ``HamiltonianMonteCarlo(mass=...)`` has them (``friction=inf``
+           is that sampler's transition with the same mass).  With a mass an ``MLPEnergy``, opted in or not, takes ``eager``.
+
 A fused-eligible call never falls back to eager: a missing library or a failing launch raises.
 """
 
@@ -43,7 +49,9 @@ from .. import _lib, _rng
 from ..core.energies import BaseModel, FusedSpec, fused_spec_for
 from ..core.sampler_base import BaseSampler
 from ..core.schedules import BaseScheduler
-from ._chain_host import (FUSED_MLP_MAX_DIM, fused_mlp_walk_fits, kept_statistics, new_outputs,  # noqa: F401
+from ..integrators.symplectic import _mass_args
+from ._chain_host import (FUSED_MLP_MAX_DIM, check_mass, fused_mlp_walk_fits, kept_statistics,  # noqa: F401
+                          kinetic_temperature, mass_forms, mass_row, new_outputs,
                           record_kept)  # (FUSED_MLP_MAX_DIM: importable from here as before)
 
 FUSED_MAX_DIM = 256  # one vector per lane (csrc/ghmc.hip)
@@ -73,6 +81,8 @@ class GeneralizedHMC(BaseSampler):
         friction: friction ``gamma > 0``; the velocity keeps ``exp(-gamma eps L)`` of itself per transition, ``inf`` is HMC.
         temperature: temperature ``T > 0``; the chains sample ``exp(-E / T)``.
         dtype, device: where the chains live.
+        mass: ``None`` (unit mass), a positive finite float, or a 1-D tensor of per-dimension masses (moved to the sampler's
+            device; its entries are not inspected).  With a mass the carried plane is the momentum ``p ~ N(0, T m)``.
 
     ``fused_mlp`` (class attribute, ``False``): set it on a sampler to send an eligible ``MLPEnergy`` call to the one-launch
     route ``fused_mlp`` (module docstring).
@@ -93,9 +103,11 @@ class GeneralizedHMC(BaseSampler):
         temperature: float = 1.0,
         dtype: torch.dtype = torch.float32,
         device: Optional[Union[str, torch.device]] = None,
+        mass: Optional[Union[float, torch.Tensor]] = None,
     ):
         super().__init__(model=model, dtype=dtype, device=device)
         self._register_param("step_size", step_size, positive=True)
+        self.mass = check_mass(mass, self.device)
         if int(n_leapfrog_steps) != n_leapfrog_steps or n_leapfrog_steps < 1:
             raise ValueError("n_leapfrog_steps must be an integer >= 1")
         if not friction > 0:  # (inf is allowed: a full refresh)
@@ -120,11 +132,13 @@ class GeneralizedHMC(BaseSampler):
         if spec is None or x.shape[1] > FUSED_MAX_DIM:
             return "eager", None
         if spec.kind == _lib.ENERGY_MLP:
+            if self.mass is not None:  # (no mass on the MLP walks)
+                return "eager", None
             dim = x.shape[1]
             if self.fused_mlp and fused_mlp_walk_fits(spec.n_comp, getattr(self.model, "in_dim", None), dim):
                 return "fused_mlp", spec
             return "eager", None
-        return "fused", spec
+        return ("fused" if self.mass is None else "fused_mass"), spec
 
     # ---------------------------------------------------------------------------------
     # public API
@@ -151,17 +165,19 @@ class GeneralizedHMC(BaseSampler):
         ``model_kwargs``: conditioning passed to the model at every evaluation; a non-empty dict takes the eager route.
 
         ``velocity``: the start velocities, shaped as ``x`` (as a call with ``return_velocity=True`` returned them: continue
-        that run); ``None`` draws them from ``N(0, T I)``.
+        that run); ``None`` draws them from ``N(0, T I)``.  A sampler with a ``mass`` carries the momentum in this plane
+        (``N(0, T m)``), here and in ``return_velocity``.
 
         Returns the final positions ``[n, *shape]`` (or, with ``return_trajectory``, the kept positions
         ``[n, n_steps // thin, *shape]``); with ``return_diagnostics`` a dict follows, holding ``"mean"`` / ``"var"``
         (``[n_kept, *shape]``, biased variance clamped to [1e-10, 1e10]), ``"energy"`` and ``"acceptance_rate"``
         (``[n_kept]``: the accepted share of each kept transition) of the kept positions and ``"kinetic_temperature"``, the
-        mean of ``v^2`` over chains and coordinates of the final velocities (``T`` in law); with ``return_velocity`` the final
+        mean of ``v^2`` (with a mass: of ``p^2 / m``) over chains and coordinates of the final velocities (``T`` in law); with ``return_velocity`` the final
         velocities come last.  The caller's ``x`` and ``velocity`` are never written.
 
         Raises:
-            ValueError: ``thin < 1``, ``x`` and ``dim`` both ``None``, or a ``velocity`` whose shape differs from the state's.
+            ValueError: ``thin < 1``, ``x`` and ``dim`` both ``None``, a ``velocity`` whose shape differs from the state's, or a
+                ``mass`` tensor whose length is not the state's last width.
         """
         if thin < 1:
             raise ValueError("thin must be >= 1")
@@ -173,9 +189,13 @@ class GeneralizedHMC(BaseSampler):
                 raise ValueError(f"velocity must have the state's shape {tuple(x.shape)}, got {tuple(velocity.shape)}")
             velocity = velocity.to(device=self.device, dtype=self.dtype)
         model_kwargs = self._prepare_model_kwargs(model_kwargs)
+        m = mass_row(self.mass, x)
         route, spec = self._route(x, model_kwargs)
         if route == "fused":
             state, v, traj, diag = self._sample_fused(x, velocity, spec, n_steps, thin, return_trajectory, return_diagnostics, generator)
+        elif route == "fused_mass":
+            state, v, traj, diag = self._sample_fused(x, velocity, spec, n_steps, thin, return_trajectory, return_diagnostics, generator,
+                                                      entry="ebm_ghmc_chain_mass_f32")
         elif route == "fused_mlp":
             state, v, traj, diag = self._sample_fused(x, velocity, spec, n_steps, thin, return_trajectory, return_diagnostics, generator,
                                                       entry="ebm_ghmc_mlp_chain_f32")
@@ -184,7 +204,7 @@ class GeneralizedHMC(BaseSampler):
                                                       model_kwargs)
         out = (traj if return_trajectory else state,)
         if return_diagnostics:
-            diag["kinetic_temperature"] = v.square().mean() if v.numel() else torch.full((), float("nan"), dtype=v.dtype, device=v.device)
+            diag["kinetic_temperature"] = kinetic_temperature(v, m)
             out += (diag,)
         if return_velocity:
             out += (v,)
@@ -236,13 +256,22 @@ class GeneralizedHMC(BaseSampler):
         traj, diag = new_outputs(x, x.shape, n_steps // thin, want_traj, want_diag, acceptance=True)
         energy = lambda x_: self._model_energy(x_, model_kwargs)  # noqa: E731
         clamped_energy = lambda x_: energy(x_).clamp_(min=-1e10, max=1e10)  # noqa: E731
-        kinetic = lambda v_: (0.5 * torch.sum(v_.flatten(1).square(), dim=-1)).clamp_(min=0.0, max=1e10)  # noqa: E731
+        massed, m = self.mass is not None, mass_row(self.mass, x)
+        if massed:  # sqrt(m) and max(m, 1e-10) per slot; the kinetic energy and the drift spelled as HamiltonianMonteCarlo's eager ones
+            m_sqrt, m_safe = mass_forms(self.mass, x)
+        if not massed:
+            kinetic = lambda v_: (0.5 * torch.sum(v_.flatten(1).square(), dim=-1)).clamp_(min=0.0, max=1e10)  # noqa: E731
+        elif isinstance(m, float):
+            kinetic = lambda p_: (0.5 * torch.sum(p_.flatten(1).square(), dim=-1) / m).clamp_(min=0.0, max=1e10)  # noqa: E731
+        else:
+            kinetic = lambda p_: (0.5 * torch.sum((p_.square() / m).flatten(1), dim=-1)).clamp_(min=0.0, max=1e10)  # noqa: E731
         force = lambda x_: (-self._model_gradient(x_, model_kwargs)).clamp_(min=-1e6, max=1e6)  # noqa: E731
         per_chain = lambda m: m.view(-1, *([1] * (x.ndim - 1)))  # noqa: E731
         n, L = x.shape[0], self.n_leapfrog_steps
         if v is None:
             sqrt_temp = ghmc_constants(1.0, 1, self.friction, self.temperature, x.dtype)[2]
-            v = sqrt_temp * self._draw_normal(x.shape, x, generator)
+            z0 = self._draw_normal(x.shape, x, generator)
+            v = (sqrt_temp * m_sqrt) * z0 if massed else sqrt_temp * z0
         keep = 0
         with self.autocast_context():
             for t in range(n_steps):
@@ -251,13 +280,13 @@ class GeneralizedHMC(BaseSampler):
                 xi = self._draw_normal(x.shape, x, generator)
                 u = self._draw_uniform(n, x, generator)
                 # every operation rounded on its own, in the order of the contract (include/ebm_hip.h)
-                v = c1 * v + c2 * xi  # O
+                v = c1 * v + (c2 * m_sqrt if massed else c2) * xi  # O (with a mass v is the momentum: N(0, T m))
                 h0 = clamped_energy(x) + kinetic(v)
                 eps_t = torch.full((), float(eps), dtype=x.dtype, device=x.device)
                 xp, vp = x, v
                 for _ in range(L):  # the safe-mode leapfrog step of integrators/symplectic.py, identity mass
                     v_half = vp + 0.5 * eps_t * force(xp)
-                    xp = xp + eps_t * v_half
+                    xp = xp + (eps_t * v_half / m_safe if massed else eps_t * v_half)
                     vp = v_half + 0.5 * eps_t * force(xp)
                     xp = xp.nan_to_num_(nan=0.0)
                     vp = vp.nan_to_num_(nan=0.0)
@@ -289,18 +318,24 @@ class GeneralizedHMC(BaseSampler):
         seed, step0 = _rng.reserve(generator, x.device, 2 * n_steps + 1)
         stream = _lib.stream_handle(x.device)
         spec_c = spec.to_c()
+        mass = ()
+        if self.mass is not None:  # (kind, scalar, pointer) directly behind `temperature`; the diagonal is kept until the launch
+            kind, m_scalar, m_diag = _mass_args(self.mass, state)
+            mass = (kind, m_scalar, _lib.ptr(m_diag))
         if n > 0 and n_steps > 0:
             _lib.call(
                 entry,
                 spec_c, _lib.ptr(state), _lib.ptr(vel), n, dim, n_steps, self.n_leapfrog_steps, self.get_scheduled_value("step_size"),
-                self.friction, self.temperature, int(draw_v0), thin, _lib.ptr(traj) if need_kept else None, _lib.ptr(mask), None, None,
+                self.friction, self.temperature, *mass, int(draw_v0), thin, _lib.ptr(traj) if need_kept else None, _lib.ptr(mask), None, None,
                 seed, step0, stream,
             )
         elif draw_v0:  # no transition: the start velocities alone, the same field
             if n > 0:
                 flat = torch.empty((n * dim + 3) // 4 * 4, dtype=torch.float32, device=x.device)
                 _lib.call("ebm_noise_fill_f32", _lib.ptr(flat), n * dim, _lib.NOISE_NORMAL, seed, step0, stream)
-                vel = ghmc_constants(1.0, 1, self.friction, self.temperature)[2] * flat[: n * dim].view(n, dim)
+                sqrt_temp = ghmc_constants(1.0, 1, self.friction, self.temperature)[2]
+                scale = sqrt_temp if self.mass is None else sqrt_temp * mass_forms(self.mass, state)[0]
+                vel = scale * flat[: n * dim].view(n, dim)
         self.advance_schedulers(n_steps)
         diag = None
         if want_diag:

@@ -25,6 +25,11 @@ Two execution routes, chosen once per ``sample()`` call (``_route``):
            recurrence in torch ops around ``model.gradient``, drawing ``randn(n, dim)`` for the start velocities and once per
            step.
 
+``fused_mass``  a sampler built with ``mass=`` (a float or a per-dimension tensor) under the conditions of ``fused``: ONE launch
+           of ``ebm_kinetic_chain_mass_f32`` (docs/design/mass.md).  The carried plane is then the MOMENTUM ``p ~ N(0, T m)``:
+           ``velocity=`` / ``return_velocity`` carry it, and the step reads ``x += (h / 2) p / m``, ``p = c1 p + c2 sqrt(m) xi``.
+           With a mass an ``MLPEnergy``, opted in or not, takes ``eager``.
+
 A fused-eligible call never falls back to eager: a missing library or a failing launch raises.
 """
 
@@ -39,7 +44,9 @@ from .. import _lib, _rng
 from ..core.energies import BaseModel, FusedSpec, fused_spec_for
 from ..core.sampler_base import BaseSampler
 from ..core.schedules import BaseScheduler
-from ._chain_host import fused_mlp_walk_fits, kept_statistics, new_outputs, record_kept
+from ..integrators.symplectic import _mass_args
+from ._chain_host import (check_mass, fused_mlp_walk_fits, kept_statistics, kinetic_temperature, mass_forms, mass_row,
+                          new_outputs, record_kept)
 
 FUSED_MAX_DIM = 256  # one vector per lane (csrc/kinetic.hip)
 
@@ -60,6 +67,8 @@ class UnderdampedLangevin(BaseSampler):
         friction: friction ``gamma > 0``.
         temperature: temperature ``T > 0``; the chains sample ``exp(-E / T)``.
         dtype, device: where the chains live.
+        mass: ``None`` (unit mass), a positive finite float, or a 1-D tensor of per-dimension masses (moved to the sampler's
+            device; its entries are not inspected).  With a mass the carried plane is the momentum ``p ~ N(0, T m)``.
     """
 
     #: opt-in: an ``MLPEnergy`` (hidden 64 / 128, ``dim == in_dim <= 128``, CUDA fp32, no autocast, a constant step size) runs as
@@ -79,9 +88,11 @@ class UnderdampedLangevin(BaseSampler):
         temperature: float = 1.0,
         dtype: torch.dtype = torch.float32,
         device: Optional[Union[str, torch.device]] = None,
+        mass: Optional[Union[float, torch.Tensor]] = None,
     ):
         super().__init__(model=model, dtype=dtype, device=device)
         self._register_param("step_size", step_size, positive=True)
+        self.mass = check_mass(mass, self.device)
         if not (friction > 0 and math.isfinite(friction)):
             raise ValueError("friction must be positive")
         if not (temperature > 0 and math.isfinite(temperature)):
@@ -103,11 +114,13 @@ class UnderdampedLangevin(BaseSampler):
         if spec is None or x.shape[1] > FUSED_MAX_DIM:
             return "eager", None
         if spec.kind == _lib.ENERGY_MLP:
+            if self.mass is not None:  # (no mass on the MLP walks)
+                return "eager", None
             dim = x.shape[1]
             if self.fused_mlp and fused_mlp_walk_fits(spec.n_comp, getattr(self.model, "in_dim", None), dim):
                 return "fused_mlp", spec
             return "eager", None
-        return "fused", spec
+        return ("fused" if self.mass is None else "fused_mass"), spec
 
     # ---------------------------------------------------------------------------------
     # public API
@@ -134,17 +147,19 @@ class UnderdampedLangevin(BaseSampler):
         ``model_kwargs``: conditioning passed to the model at every evaluation; a non-empty dict takes the eager route.
 
         ``velocity``: the start velocities, shaped as ``x`` (as a call with ``return_velocity=True`` returned them: continue
-        that run); ``None`` draws them from ``N(0, T I)``.
+        that run); ``None`` draws them from ``N(0, T I)``.  A sampler with a ``mass`` carries the momentum in this plane
+        (``N(0, T m)``), here and in ``return_velocity``.
 
         Returns the final positions ``[n, *shape]`` (or, with ``return_trajectory``, the kept positions
         ``[n, n_steps // thin, *shape]``); with ``return_diagnostics`` a dict follows, holding ``"mean"`` / ``"var"``
         (``[n_kept, *shape]``, biased variance clamped to [1e-10, 1e10]) and ``"energy"`` (``[n_kept]``) of the kept
-        positions and ``"kinetic_temperature"``, the mean of ``v^2`` over chains and coordinates of the final velocities -- an
+        positions and ``"kinetic_temperature"``, the mean of ``v^2`` (with a mass: of ``p^2 / m``) over chains and coordinates of the final velocities -- an
         estimate of ``T (1 - h^2 E'' / 4)``, a cheap check of the step size; with ``return_velocity`` the final velocities
         come last.  The caller's ``x`` and ``velocity`` are never written.
 
         Raises:
-            ValueError: ``thin < 1``, ``x`` and ``dim`` both ``None``, or a ``velocity`` whose shape differs from the state's.
+            ValueError: ``thin < 1``, ``x`` and ``dim`` both ``None``, a ``velocity`` whose shape differs from the state's, or a
+                ``mass`` tensor whose length is not the state's last width.
         """
         if thin < 1:
             raise ValueError("thin must be >= 1")
@@ -156,9 +171,13 @@ class UnderdampedLangevin(BaseSampler):
                 raise ValueError(f"velocity must have the state's shape {tuple(x.shape)}, got {tuple(velocity.shape)}")
             velocity = velocity.to(device=self.device, dtype=self.dtype)
         model_kwargs = self._prepare_model_kwargs(model_kwargs)
+        m = mass_row(self.mass, x)
         route, spec = self._route(x, model_kwargs)
         if route == "fused":
             state, v, traj, diag = self._sample_fused(x, velocity, spec, n_steps, thin, return_trajectory, return_diagnostics, generator)
+        elif route == "fused_mass":
+            state, v, traj, diag = self._sample_fused(x, velocity, spec, n_steps, thin, return_trajectory, return_diagnostics, generator,
+                                                      entry="ebm_kinetic_chain_mass_f32")
         elif route == "fused_mlp":
             state, v, traj, diag = self._sample_fused(x, velocity, spec, n_steps, thin, return_trajectory, return_diagnostics, generator,
                                                       entry="ebm_kinetic_mlp_chain_f32")
@@ -167,7 +186,7 @@ class UnderdampedLangevin(BaseSampler):
                                                       model_kwargs)
         out = (traj if return_trajectory else state,)
         if return_diagnostics:
-            diag["kinetic_temperature"] = v.square().mean() if v.numel() else torch.full((), float("nan"), dtype=v.dtype, device=v.device)
+            diag["kinetic_temperature"] = kinetic_temperature(v, m)
             out += (diag,)
         if return_velocity:
             out += (v,)
@@ -212,20 +231,27 @@ class UnderdampedLangevin(BaseSampler):
         model_kwargs = model_kwargs or {}
         traj, diag = new_outputs(x, x.shape, n_steps // thin, want_traj, want_diag)
         energy = lambda x_: self._model_energy(x_, model_kwargs)  # noqa: E731
+        massed = self.mass is not None
+        if massed:  # the per-slot forms of the contract: sqrt(m) and max(m, 1e-10), in the state's dtype
+            m_sqrt, m_safe = mass_forms(self.mass, x)
         if v is None:
             sqrt_temp = baoab_constants(1.0, self.friction, self.temperature, x.dtype)[3]
-            v = sqrt_temp * torch.randn(x.shape, dtype=x.dtype, device=x.device, generator=generator)
+            z0 = torch.randn(x.shape, dtype=x.dtype, device=x.device, generator=generator)
+            v = (sqrt_temp * m_sqrt) * z0 if massed else sqrt_temp * z0
         keep = 0
         with self.autocast_context():
             g = self._model_gradient(x, model_kwargs)
             for s in range(n_steps):
                 hh, c1, c2, _ = baoab_constants(self.get_scheduled_value("step_size"), self.friction, self.temperature, x.dtype)
                 xi = torch.randn(x.shape, dtype=x.dtype, device=x.device, generator=generator)
-                # every operation rounded on its own, in the order of the contract (include/ebm_hip.h)
+                # every operation rounded on its own, in the order of the contract (include/ebm_hip.h); with a mass v is the
+                # momentum, the drift runs on a = hh / m_safe and the refresh on s = c2 * m_sqrt
+                # (a true division: torch spells `float / tensor` as reciprocal-then-multiply, two roundings)
+                a, sc = (torch.full_like(m_safe, hh) / m_safe, c2 * m_sqrt) if massed else (hh, c2)
                 v = v - hh * g
-                x = x + hh * v
-                v = c1 * v + c2 * xi
-                x = x + hh * v
+                x = x + a * v
+                v = c1 * v + sc * xi
+                x = x + a * v
                 g = self._model_gradient(x, model_kwargs)
                 v = v - hh * g
                 self.step_schedulers()
@@ -250,17 +276,23 @@ class UnderdampedLangevin(BaseSampler):
         seed, step0 = _rng.reserve(generator, x.device, n_steps + 1)
         stream = _lib.stream_handle(x.device)
         spec_c = spec.to_c()
+        mass = ()
+        if self.mass is not None:  # (kind, scalar, pointer) directly behind `temperature`; the diagonal is kept until the launch
+            kind, m_scalar, m_diag = _mass_args(self.mass, state)
+            mass = (kind, m_scalar, _lib.ptr(m_diag))
         if n > 0 and n_steps > 0:
             _lib.call(
                 entry,
                 spec_c, _lib.ptr(state), _lib.ptr(vel), n, dim, n_steps, self.get_scheduled_value("step_size"), self.friction,
-                self.temperature, int(draw_v0), thin, _lib.ptr(traj) if need_kept else None, None, seed, step0, stream,
+                self.temperature, *mass, int(draw_v0), thin, _lib.ptr(traj) if need_kept else None, None, seed, step0, stream,
             )
         elif draw_v0:  # no step: the start velocities alone, the same field
             if n > 0:
                 flat = torch.empty((n * dim + 3) // 4 * 4, dtype=torch.float32, device=x.device)
                 _lib.call("ebm_noise_fill_f32", _lib.ptr(flat), n * dim, _lib.NOISE_NORMAL, seed, step0, stream)
-                vel = baoab_constants(1.0, self.friction, self.temperature)[3] * flat[: n * dim].view(n, dim)
+                sqrt_temp = baoab_constants(1.0, self.friction, self.temperature)[3]
+                scale = sqrt_temp if self.mass is None else sqrt_temp * mass_forms(self.mass, state)[0]
+                vel = scale * flat[: n * dim].view(n, dim)
         self.advance_schedulers(n_steps)
         diag = None
         if want_diag:

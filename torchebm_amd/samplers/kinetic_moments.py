@@ -20,6 +20,8 @@ Three execution routes, chosen once per call:
            Philox draws, with the same reservation, so the final ``x`` and ``v`` are that ``sample(return_velocity=True)``'s
            bit for bit; the energies are the kernel's, not autograd's; the acceptance as above.  With ``fused_mlp`` alone
            the call stays on ``eager`` and returns what it always did.
+           A sampler with a ``mass`` is never sent here: its route is ``fused_mass``, which stays step by step (below), one
+           launch of the massed chain entry per transition.
 ``eager``  anything else, CPU included: the sampler's own ``sample(n_steps=1, velocity=v, return_velocity=True)`` per
            transition around :class:`RunningMoments`, with the same reciprocal table; the ``v^2`` mean by the same recurrence
            in the state's dtype.
@@ -32,6 +34,7 @@ from __future__ import annotations
 import torch
 
 from .. import _lib, _rng
+from ._chain_host import mass_row
 from .moments import ChainMoments, RunningMoments, recip_table, split_counted
 
 SAMPLER_BAOAB, SAMPLER_GHMC = 0, 1
@@ -62,6 +65,7 @@ def _eager(sampler, ghmc, x, v, k, burn_in, h, energy, generator):
     acc = RunningMoments(h, with_energy=energy)
     v2 = None if ghmc else torch.zeros((2, *x.shape), dtype=x.dtype, device=x.device)
     rates = []
+    mass = mass_row(getattr(sampler, "mass", None), x)
     for s in range(k):
         out = sampler.sample(x=x, n_steps=1, return_diagnostics=ghmc, reset_schedulers=False, velocity=v, return_velocity=True,
                              generator=generator)
@@ -73,9 +77,10 @@ def _eager(sampler, ghmc, x, v, k, burn_in, h, energy, generator):
         if s >= burn_in:
             half, c = divmod(s - burn_in, h)
             acc.add(x, sampler._model_energy(x, {}) if energy else None)
-            if v2 is not None:  # m = m + (v v - m) recip[c - 1], every operation rounded on its own
+            if v2 is not None:  # m = m + (v v - m) recip[c - 1], every operation rounded on its own; with a mass v v is p p / m
                 rc = acc.recip[c].to(dtype=x.dtype).item()
-                v2[half] = v2[half] + (v * v - v2[half]) * rc
+                vv = v * v if mass is None else v * v / mass
+                v2[half] = v2[half] + (vv - v2[half]) * rc
     rate = torch.stack(rates).to(torch.float32) if ghmc else None
     res = ChainMoments(acc.mean, acc.m2, h, acc.e_mean, acc.e_m2, rate, v2)
     return x, v, res

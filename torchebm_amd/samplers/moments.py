@@ -187,6 +187,15 @@ class ChainMoments:
         when the run kept no ``velocity_sq_mean``.  Under BAOAB on a quadratic energy it estimates ``T (1 - h^2 E'' / 4)``."""
         return self._compute().get("kinetic_temperature")
 
+    def diagonal_mass(self) -> torch.Tensor:
+        """``1 / var`` as a float32 ``[dim]`` tensor on the moments' device: the textbook diagonal mass for the ``mass=`` of
+        ``HamiltonianMonteCarlo``, ``UnderdampedLangevin`` and ``GeneralizedHMC`` (a coordinate of standard deviation ``s`` then
+        moves as one of unit scale).  Raises ``ValueError`` when a pooled variance is not finite and positive."""
+        var = self._compute()["var"].reshape(-1)
+        if not bool((torch.isfinite(var) & (var > 0)).all()):
+            raise ValueError("diagonal_mass: a pooled variance is not finite and positive (run longer, or drop the chains that left)")
+        return (1.0 / var).to(torch.float32)
+
     def __getattr__(self, name):
         if name.startswith("_") or name in ("chain_mean", "chain_m2", "energy_mean", "energy_m2", "half_len", "acceptance_rate",
                                             "velocity_sq_mean"):
