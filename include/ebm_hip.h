@@ -772,7 +772,8 @@ EBM_API int ebm_kinetic_chain_mass_f32(const ebm_energy_t* energy, float* x, flo
  * Refusals, all in front of any device access and of the early return for n_chains == 0: a NULL energy, x or v, k_steps < 1,
  * thin < 1, h, gamma or temperature not positive and finite (EBM_EINVAL); a kind other than EBM_ENERGY_MLP (EBM_EKIND); a
  * hidden width (energy->n_comp) other than 64 / 128 or dim outside 1 .. 128 (EBM_EDIM).  No H = 256, no pre-split W1 image
- * (energy->aux is ignored), no clamp, no tables, no mass matrix, no diagnostics records.
+ * (energy->aux is ignored), no clamp, no tables, unit mass (a scalar or diagonal mass: ebm_kinetic_mlp_chain_mass_f32,
+ * ebm_hip_mass_mlp.h), no diagnostics records.
  */
 EBM_API int ebm_kinetic_mlp_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim,
                                       int32_t k_steps, double h, double gamma, double temperature, int32_t draw_v0,
@@ -897,7 +898,8 @@ EBM_API int ebm_ghmc_chain_mass_f32(const ebm_energy_t* energy, float* x, float*
  * n_leapfrog < 1, thin < 1, n_chains < 0, eps, gamma or temperature not positive, or NaN, a non-finite eps or temperature
  * (EBM_EINVAL; gamma = +inf is allowed); a kind other than EBM_ENERGY_MLP (EBM_EKIND); a hidden width (energy->n_comp) other than
  * 64 / 128 or dim outside 1 .. 128 (EBM_EDIM, the message names both).  x, v, traj and noise must be 16-byte aligned.  No
- * H = 256, no pre-split W1 image (energy->aux is ignored), no tables, no mass matrix, no diagnostics records.
+ * H = 256, no pre-split W1 image (energy->aux is ignored), no tables, unit mass (a scalar or
+ * diagonal mass: ebm_ghmc_mlp_chain_mass_f32, ebm_hip_mass_mlp.h), no diagnostics records.
  */
 EBM_API int ebm_ghmc_mlp_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t n_mh,
                                    int32_t n_leapfrog, double eps, double gamma, double temperature, int32_t draw_v0,

@@ -90,6 +90,13 @@ EXPORTS = (
     "ebm_gmm_active_columns_i32",
 )
 
+#: entry points declared in include/ebm_hip_mass_mlp.h, the companion header of the massed walks on the MLP energy (the same
+#: library, the same ABI version; tests/test_mass_mlp.py checks the library exports both)
+EXPORTS_MASS_MLP = (
+    "ebm_kinetic_mlp_chain_mass_f32",
+    "ebm_ghmc_mlp_chain_mass_f32",
+)
+
 #: number of calls made through each entry point in this process (tests use it to
 #: prove that a GPU test really went through the HIP library)
 call_counts: Counter = Counter()
@@ -184,6 +191,11 @@ _PROTOTYPES = {
     ),
     # (the same parameter list, on the MLP energy)
     "ebm_kinetic_mlp_chain_f32": (C.c_int, [_ENERGY_P, _p, _p, _i64, _i32, _i32, _d, _d, _d, _i32, _i32, _p, _p, _u64, _u64, _p]),
+    # (... on the MLP energy, with the same three behind `temperature`)
+    "ebm_kinetic_mlp_chain_mass_f32": (
+        C.c_int,
+        [_ENERGY_P, _p, _p, _i64, _i32, _i32, _d, _d, _d, _i32, _d, _p, _i32, _i32, _p, _p, _u64, _u64, _p],
+    ),
     "ebm_ghmc_chain_f32": (
         C.c_int,
         [_ENERGY_P, _p, _p, _i64, _i32, _i32, _i32, _d, _d, _d, _i32, _i32, _p, _p, _p, _p, _u64, _u64, _p],
@@ -195,6 +207,10 @@ _PROTOTYPES = {
     "ebm_ghmc_mlp_chain_f32": (
         C.c_int,
         [_ENERGY_P, _p, _p, _i64, _i32, _i32, _i32, _d, _d, _d, _i32, _i32, _p, _p, _p, _p, _u64, _u64, _p],
+    ),
+    "ebm_ghmc_mlp_chain_mass_f32": (  # ... with the same three behind `temperature`
+        C.c_int,
+        [_ENERGY_P, _p, _p, _i64, _i32, _i32, _i32, _d, _d, _d, _i32, _d, _p, _i32, _i32, _p, _p, _p, _p, _u64, _u64, _p],
     ),
     "ebm_kinetic_moments_f32": (
         C.c_int,

@@ -6,6 +6,7 @@
 #include <cstdlib>
 
 #include "chain_launch.h"
+#include "../../include/ebm_hip_mass_mlp.h"  // the two massed MLP walks' declarations (a companion of ebm_hip.h)
 
 namespace ebm {
 
@@ -613,7 +614,7 @@ int ebm_chain_moments_mlp_f32(const ebm_energy_t* energy, float* x, int64_t n_ch
   return langevin_moments_mlp_chain_launch(q, (hipStream_t)stream);
 }
 
-// What the two massed entries ask of their mass (the forms of ebm_hmc_chain_f32; EBM_MASS_NONE belongs to the unit-mass entries)
+// What the massed entries ask of their mass (the forms of ebm_hmc_chain_f32; EBM_MASS_NONE belongs to the unit-mass entries)
 static int check_chain_mass(const ChainMass& m, const char* who) {
   if (m.kind != EBM_MASS_SCALAR && m.kind != EBM_MASS_DIAG)
     return fail(EBM_EINVAL, "%s: mass_kind=%d (EBM_MASS_SCALAR or EBM_MASS_DIAG; the unit-mass entry takes no mass)", who, m.kind);
@@ -642,7 +643,9 @@ static int kinetic_chain_impl(const char* who, bool mlp, const ebm_energy_t* ene
                               const float* noise, uint64_t seed, uint64_t offset, void* stream, const ChainMass* mass = nullptr) {
   if (!mlp && energy && energy->kind == EBM_ENERGY_MLP)
     return fail(EBM_EKIND, "%s: the MLP energy has no underdamped-Langevin kernel (the sampler's eager route takes it)", who);
-  if (int r = mlp ? check_mlp_walk(energy, dim, who, "ebm_kinetic_chain_f32") : check_energy(energy, dim, who)) return r;
+  if (int r = mlp ? check_mlp_walk(energy, dim, who, mass ? "ebm_kinetic_chain_mass_f32" : "ebm_kinetic_chain_f32")
+                  : check_energy(energy, dim, who))
+    return r;
   if (!mlp) {
     if (int r = check_state(x, n_chains, dim, who)) return r;
   } else if (!x) {
@@ -662,7 +665,10 @@ static int kinetic_chain_impl(const char* who, bool mlp, const ebm_energy_t* ene
     return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
   const KineticChainReq q = kinetic_request(energy, x, v, n_chains, dim, k_steps, h, gamma, temperature, draw_v0, thin, traj, noise,
                                             seed, offset);
-  if (mass) return kinetic_mass_chain_launch(KineticMassChainReq{q, *mass}, (hipStream_t)stream);
+  if (mass) {
+    const KineticMassChainReq m{q, *mass};
+    return mlp ? kinetic_mass_mlp_chain_launch(m, (hipStream_t)stream) : kinetic_mass_chain_launch(m, (hipStream_t)stream);
+  }
   return mlp ? kinetic_mlp_chain_launch(q, (hipStream_t)stream) : kinetic_chain_launch(q, (hipStream_t)stream);
 }
 
@@ -687,6 +693,15 @@ int ebm_kinetic_mlp_chain_f32(const ebm_energy_t* energy, float* x, float* v, in
                               const float* noise, uint64_t seed, uint64_t offset, void* stream) {
   return kinetic_chain_impl("ebm_kinetic_mlp_chain_f32", true, energy, x, v, n_chains, dim, k_steps, h, gamma, temperature, draw_v0,
                             thin, traj, noise, seed, offset, stream);
+}
+
+int ebm_kinetic_mlp_chain_mass_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t k_steps,
+                                   double h, double gamma, double temperature, int32_t mass_kind, double mass_scalar,
+                                   const float* mass_diag, int32_t draw_v0, int32_t thin, float* traj, const float* noise,
+                                   uint64_t seed, uint64_t offset, void* stream) {
+  const ChainMass mass{mass_kind, mass_scalar, mass_diag};
+  return kinetic_chain_impl("ebm_kinetic_mlp_chain_mass_f32", true, energy, x, v, n_chains, dim, k_steps, h, gamma, temperature,
+                            draw_v0, thin, traj, noise, seed, offset, stream, &mass);
 }
 
 // The request of both generalized-HMC entries: the constants of the refresh over one trajectory's time eps L, formed in double,
@@ -779,6 +794,32 @@ int ebm_ghmc_mlp_chain_f32(const ebm_energy_t* energy, float* x, float* v, int64
   return ghmc_mlp_chain_launch(ghmc_request(energy, x, v, n_chains, dim, n_mh, n_leapfrog, eps, gamma, temperature, draw_v0, thin,
                                             traj, accept_mask, noise, u, seed, offset),
                                (hipStream_t)stream);
+}
+
+// (the checks of ebm_ghmc_mlp_chain_f32 in its order, the mass behind the shape rule and in front of the empty call)
+int ebm_ghmc_mlp_chain_mass_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t n_mh,
+                                int32_t n_leapfrog, double eps, double gamma, double temperature, int32_t mass_kind,
+                                double mass_scalar, const float* mass_diag, int32_t draw_v0, int32_t thin, float* traj,
+                                uint8_t* accept_mask, const float* noise, const float* u, uint64_t seed, uint64_t offset,
+                                void* stream) {
+  const char* who = "ebm_ghmc_mlp_chain_mass_f32";
+  if (int r = check_mlp_walk(energy, dim, who, "ebm_ghmc_chain_mass_f32")) return r;
+  // (the dim range is wide_mlp_check_shape's to refuse)
+  if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
+  if (!v) return fail(EBM_EINVAL, "%s: velocity pointer is NULL", who);
+  if (n_chains < 0) return fail(EBM_EINVAL, "%s: bad shape [%lld, %d]", who, (long long)n_chains, dim);
+  if (int r = check_ghmc_parameters(n_mh, n_leapfrog, thin, eps, gamma, temperature, who)) return r;
+  if (int r = wide_mlp_check_shape(who, energy->n_comp, dim)) return r;
+  const ChainMass mass{mass_kind, mass_scalar, mass_diag};
+  if (int r = check_chain_mass(mass, who)) return r;
+  if (n_chains == 0) return 0;
+  if (!aligned16(x) || !aligned16(v) || (traj && !aligned16(traj)) || (noise && !aligned16(noise)))
+    return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  return ghmc_mass_mlp_chain_launch(GhmcMassChainReq{ghmc_request(energy, x, v, n_chains, dim, n_mh, n_leapfrog, eps, gamma,
+                                                                  temperature, draw_v0, thin, traj, accept_mask, noise, u, seed,
+                                                                  offset),
+                                                     mass},
+                                    (hipStream_t)stream);
 }
 
 // Both running-moments entries of the two walkers, as the underdamped pair; the analytic entry's geometry stands in front of its

@@ -426,6 +426,9 @@ int ghmc_mlp_chain_launch(const GhmcChainReq&, hipStream_t);
 // ---------------------------------------------------------------------------------
 int kinetic_mass_chain_launch(const KineticMassChainReq&, hipStream_t);
 int ghmc_mass_chain_launch(const GhmcMassChainReq&, hipStream_t);
+// ... on the MLP energy (mlp_wide_kinetic_mass.hip, mlp_wide_ghmc_mass.hip: the same requests; the walks of the two MLP entries above, the mass forms in LDS tables read a register quad at a time)
+int kinetic_mass_mlp_chain_launch(const KineticMassChainReq&, hipStream_t);
+int ghmc_mass_mlp_chain_launch(const GhmcMassChainReq&, hipStream_t);
 
 // ---------------------------------------------------------------------------------
 // Running moments of the two (kinetic_moments.hip: the BAOAB or the GHMC walker with Welford pairs beside position and velocity)

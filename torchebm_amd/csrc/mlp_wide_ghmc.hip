@@ -4,7 +4,8 @@
 // Shapes: hidden width 64 / 128, dim <= 128 -- HT in {2, 4} x DT in {1 .. 4} at wide_mode(HT, DT): split-bf16 images in LDS
 // (MODE 2), fp32 weights in LDS at H = 128 above dim 64 (MODE 0).  This unit holds the H = 64 kernels and the dispatch,
 // mlp_wide_ghmc_h128.hip the H = 128 kernels.  Not built: H = 256 (STREAM), the slab mode (MODE 3), the THIN mode (MODE 4),
-// FAST variants, diagnostics records, a mass matrix, tables.
+// FAST variants, diagnostics records, tables.  A scalar or diagonal mass is a kernel family of its own,
+// mlp_wide_ghmc_mass.hip: this unit never sees a mass.
 #include "chain_launch.h"
 #include "mlp_wide_ghmc_body.h"
 

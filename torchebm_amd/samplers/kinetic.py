@@ -28,7 +28,10 @@ Two execution routes, chosen once per ``sample()`` call (``_route``):
 ``fused_mass``  a sampler built with ``mass=`` (a float or a per-dimension tensor) under the conditions of ``fused``: ONE launch
            of ``ebm_kinetic_chain_mass_f32`` (docs/design/mass.md).  The carried plane is then the MOMENTUM ``p ~ N(0, T m)``:
            ``velocity=`` / ``return_velocity`` carry it, and the step reads ``x += (h / 2) p / m``, ``p = c1 p + c2 sqrt(m) xi``.
-           With a mass an ``MLPEnergy``, opted in or not, takes ``eager``.
+           With a mass an ``MLPEnergy`` takes ``eager`` unless both opt-ins below are set.
+``fused_mlp_mass``  opt-in twice (``sampler.fused_mlp = True`` and ``sampler.fused_mlp_mass = True``): a sampler built with
+           ``mass=`` under the conditions of ``fused_mlp``: ONE launch of ``ebm_kinetic_mlp_chain_mass_f32``
+           (docs/design/mass_mlp.md), the momentum plane and the Philox steps as on ``fused_mass`` / ``fused_mlp``.
 
 A fused-eligible call never falls back to eager: a missing library or a failing launch raises.
 """
@@ -79,6 +82,10 @@ class UnderdampedLangevin(BaseSampler):
     #: ``sample_moments`` is ONE launch of ``ebm_kinetic_moments_mlp_f32`` (docs/design/kinetic_moments_mlp.md).  Off by default: with
     #: ``fused_mlp`` alone ``sample_moments`` keeps the step-by-step recurrence and autograd's energies.
     fused_mlp_moments = False
+    #: third opt-in, read by ``sample`` of a sampler built with ``mass=``: with ``fused_mlp`` set too, an eligible ``MLPEnergy`` call
+    #: is ONE launch of ``ebm_kinetic_mlp_chain_mass_f32`` (docs/design/mass_mlp.md).  Off by default: with ``fused_mlp`` alone a
+    #: massed sampler on an ``MLPEnergy`` keeps the eager route and its bits.
+    fused_mlp_mass = False
 
     def __init__(
         self,
@@ -114,12 +121,10 @@ class UnderdampedLangevin(BaseSampler):
         if spec is None or x.shape[1] > FUSED_MAX_DIM:
             return "eager", None
         if spec.kind == _lib.ENERGY_MLP:
-            if self.mass is not None:  # (no mass on the MLP walks)
-                return "eager", None
-            dim = x.shape[1]
-            if self.fused_mlp and fused_mlp_walk_fits(spec.n_comp, getattr(self.model, "in_dim", None), dim):
-                return "fused_mlp", spec
-            return "eager", None
+            fits = self.fused_mlp and fused_mlp_walk_fits(spec.n_comp, getattr(self.model, "in_dim", None), x.shape[1])
+            if self.mass is not None:  # (a second opt-in: with fused_mlp alone a massed MLP sampler stays eager)
+                return ("fused_mlp_mass", spec) if fits and self.fused_mlp_mass else ("eager", None)
+            return ("fused_mlp", spec) if fits else ("eager", None)
         return ("fused" if self.mass is None else "fused_mass"), spec
 
     # ---------------------------------------------------------------------------------
@@ -181,6 +186,9 @@ class UnderdampedLangevin(BaseSampler):
         elif route == "fused_mlp":
             state, v, traj, diag = self._sample_fused(x, velocity, spec, n_steps, thin, return_trajectory, return_diagnostics, generator,
                                                       entry="ebm_kinetic_mlp_chain_f32")
+        elif route == "fused_mlp_mass":
+            state, v, traj, diag = self._sample_fused(x, velocity, spec, n_steps, thin, return_trajectory, return_diagnostics, generator,
+                                                      entry="ebm_kinetic_mlp_chain_mass_f32")
         else:
             state, v, traj, diag = self._sample_eager(x, velocity, n_steps, thin, return_trajectory, return_diagnostics, generator,
                                                       model_kwargs)

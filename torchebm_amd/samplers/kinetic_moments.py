@@ -20,8 +20,8 @@ Three execution routes, chosen once per call:
            Philox draws, with the same reservation, so the final ``x`` and ``v`` are that ``sample(return_velocity=True)``'s
            bit for bit; the energies are the kernel's, not autograd's; the acceptance as above.  With ``fused_mlp`` alone
            the call stays on ``eager`` and returns what it always did.
-           A sampler with a ``mass`` is never sent here: its route is ``fused_mass``, which stays step by step (below), one
-           launch of the massed chain entry per transition.
+           A sampler with a ``mass`` is never sent here: its route is ``fused_mass`` -- or ``fused_mlp_mass``, an opted-in massed
+           sampler on an ``MLPEnergy`` --, which stays step by step (below), one launch of the massed chain entry per transition.
 ``eager``  anything else, CPU included: the sampler's own ``sample(n_steps=1, velocity=v, return_velocity=True)`` per
            transition around :class:`RunningMoments`, with the same reciprocal table; the ``v^2`` mean by the same recurrence
            in the state's dtype.
