@@ -97,6 +97,11 @@ EXPORTS_MASS_MLP = (
     "ebm_ghmc_mlp_chain_mass_f32",
 )
 
+#: the entry point declared in include/ebm_hip_adapt.h, the companion header of the step-size adaptation (the same library, the
+#: same ABI version; tests/test_adapt.py checks the library exports it)
+EXPORTS_ADAPT = ("ebm_ghmc_adapt_chain_f32",)
+DA_INIT, DA_OPEN = 1, 2  # the bits of its `init_da`
+
 #: number of calls made through each entry point in this process (tests use it to
 #: prove that a GPU test really went through the HIP library)
 call_counts: Counter = Counter()
@@ -211,6 +216,11 @@ _PROTOTYPES = {
     "ebm_ghmc_mlp_chain_mass_f32": (  # ... with the same three behind `temperature`
         C.c_int,
         [_ENERGY_P, _p, _p, _i64, _i32, _i32, _i32, _d, _d, _d, _i32, _d, _p, _i32, _i32, _p, _p, _p, _p, _u64, _u64, _p],
+    ),
+    "ebm_ghmc_adapt_chain_f32": (  # ebm_ghmc_chain_f32's with eleven parameters, eps0 .. alpha_mean, in the place of `eps`
+        C.c_int,
+        [_ENERGY_P, _p, _p, _i64, _i32, _i32, _i32, _d, _d, _d, _d, _d, _i32, _i32, _p, _p, _p, _p, _d, _d, _i32, _i32, _p, _p, _p,
+         _p, _u64, _u64, _p],
     ),
     "ebm_kinetic_moments_f32": (
         C.c_int,

@@ -1,0 +1,15 @@
+// The adapting generalized-HMC kernels of ONE energy kind (ghmc_adapt_kernel.h).  The Makefile compiles this source once per
+// kind (-DEBM_UNIT_KIND=...) into ghmc_adapt_<kind>.o, so that the kinds build in parallel.
+#include "ghmc_adapt_kernel.h"
+
+namespace ebm {
+namespace ghmc_adapt {
+
+template <int KIND>
+void launch_kind(const Geometry& geo, dim3 grid, size_t smem, hipStream_t st, const GhmcAdaptArgs& a) {
+  EBM_GEO_LAUNCH_NV1(ghmc_adapt_chain, KIND, geo, grid, dim3(kBlock), smem, st, a);  // ghmc_adapt.hip refuses wider rows
+}
+template void launch_kind<EBM_UNIT_KIND>(const Geometry&, dim3, size_t, hipStream_t, const GhmcAdaptArgs&);
+
+}  // namespace ghmc_adapt
+}  // namespace ebm

@@ -1,5 +1,6 @@
 """Samplers (reference package: torchebm/samplers)."""
 
+from .adapt import StepSizeAdaptation
 from .ais import AISResult, AnnealedImportanceSampling
 from .descent import GradientDescentSampler, NesterovSampler
 from .ghmc import GeneralizedHMC
@@ -11,4 +12,4 @@ from .tempering import ReplicaExchangeHMC, ReplicaExchangeLangevin
 
 __all__ = ["LangevinDynamics", "HamiltonianMonteCarlo", "GradientDescentSampler", "NesterovSampler",
            "ReplicaExchangeLangevin", "ReplicaExchangeHMC", "AnnealedImportanceSampling", "AISResult", "ChainMoments", "RunningMoments",
-           "UnderdampedLangevin", "GeneralizedHMC"]
+           "UnderdampedLangevin", "GeneralizedHMC", "StepSizeAdaptation"]

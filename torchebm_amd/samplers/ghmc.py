@@ -249,6 +249,28 @@ class GeneralizedHMC(BaseSampler):
 
         return sample_moments(self, True, x, dim, n_steps, n_samples, burn_in, energy, velocity, return_velocity, generator)
 
+    def adapt_step_size(self, x=None, dim=None, n_steps=200, n_samples=1, target_accept=0.8, init_step_size=None, t0=10.0, gamma=0.05,
+                        kappa=0.75, mu_factor=10.0, bounds=(1e-6, 1e3), velocity=None, generator=None, apply=True):
+        """Find the leapfrog step size by dual averaging (Hoffman & Gelman 2014, section 3.2; ``samplers/adapt.py``): run
+        ``n_steps`` transitions in which EVERY CHAIN ADAPTS ITS OWN STEP SIZE towards the acceptance ``target_accept``, then pool.
+
+        ``init_step_size``: where every chain starts (``None``: the sampler's current step size); the iterates shrink towards
+        ``mu = log(mu_factor * init_step_size)``.  ``t0``, ``gamma``, ``kappa``: the dual-averaging constants (the defaults are
+        Stan's).  ``bounds``: every step size stays inside.  ``velocity``: the start velocities, as in ``sample``.
+
+        Returns a :class:`StepSizeAdaptation`: the chains behind the run (``x``, ``velocity``), ``step_sizes`` and ``acceptance``
+        per chain, and ``step_size``, a 0-dim tensor: ``exp(median(log step_sizes))`` over the chains whose value is finite.
+        ``apply=True`` sets the sampler's step size to that value, as the constructor would with a float -- ONE host read;
+        ``apply=False`` reads nothing back.  A production run at the adapted step accepts somewhat MORE than ``target_accept``
+        (the averaged iterate is not the last one).  On the fused route (module docstring of ``samplers/adapt.py``) the call is
+        ONE launch of ``ebm_ghmc_adapt_chain_f32``; a mass, a scheduler, the MLP energy, wider rows and the CPU run the same
+        recurrence in torch ops.  The caller's ``x`` and ``velocity`` are never written.
+        """
+        from .adapt import adapt_step_size
+
+        return adapt_step_size(self, self.friction, self.temperature, x, dim, n_steps, n_samples, target_accept, init_step_size, t0,
+                               gamma, kappa, mu_factor, bounds, velocity, generator, apply)
+
     # ---------------------------------------------------------------------------------
     # route: torch ops
     # ---------------------------------------------------------------------------------

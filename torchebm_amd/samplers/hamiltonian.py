@@ -235,6 +235,27 @@ class HamiltonianMonteCarlo(BaseSampler):
 
         return sample_moments(self, True, x, dim, n_steps, n_samples, burn_in, energy, generator)
 
+    def adapt_step_size(self, x=None, dim=None, n_steps=200, n_samples=1, target_accept=0.8, init_step_size=None, t0=10.0, gamma=0.05,
+                        kappa=0.75, mu_factor=10.0, bounds=(1e-6, 1e3), velocity=None, generator=None, apply=True):
+        """Find the leapfrog step size by dual averaging: ``GeneralizedHMC.adapt_step_size`` (its docstring) with a full momentum
+        refresh and ``T = 1`` -- this sampler's transition.  Every chain adapts its own step size; the returned
+        :class:`StepSizeAdaptation` carries them and their pooled value ``step_size``, which ``apply=True`` (ONE host read) makes
+        the sampler's.  On the fused route (CUDA fp32, an analytic energy, ``dim <= 256``, ``mass is None``, a constant step size,
+        the plain leapfrog integrator) the call is ONE launch of ``ebm_ghmc_adapt_chain_f32`` with ``gamma = inf``; anything else
+        runs the recurrence in torch ops with the safe-mode leapfrog step, drawing ``randn(n, dim)`` for the (discarded) start
+        velocities when none are passed, then ``randn(n, dim)`` and ``rand(n)`` per transition.
+
+        Raises:
+            ValueError: a symplectic integrator other than the plain leapfrog (the recurrence spells that step), or what
+                ``GeneralizedHMC.adapt_step_size`` refuses.
+        """
+        from .adapt import adapt_step_size
+
+        if type(self.integrator) is not LeapfrogIntegrator:
+            raise ValueError("adapt_step_size needs the plain leapfrog integrator")
+        return adapt_step_size(self, math.inf, 1.0, x, dim, n_steps, n_samples, target_accept, init_step_size, t0, gamma, kappa,
+                               mu_factor, bounds, velocity, generator, apply)
+
     # ---------------------------------------------------------------------------------
     # route: per-transition loop
     # ---------------------------------------------------------------------------------
