@@ -102,6 +102,10 @@ EXPORTS_MASS_MLP = (
 EXPORTS_ADAPT = ("ebm_ghmc_adapt_chain_f32",)
 DA_INIT, DA_OPEN = 1, 2  # the bits of its `init_da`
 
+#: the entry point declared in include/ebm_hip_adapt_mass.h, the companion header of the step-size adaptation under a mass (the
+#: same library, the same ABI version; tests/test_adapt_mass.py checks the library exports it)
+EXPORTS_ADAPT_MASS = ("ebm_ghmc_adapt_chain_mass_f32",)
+
 #: number of calls made through each entry point in this process (tests use it to
 #: prove that a GPU test really went through the HIP library)
 call_counts: Counter = Counter()
@@ -221,6 +225,11 @@ _PROTOTYPES = {
         C.c_int,
         [_ENERGY_P, _p, _p, _i64, _i32, _i32, _i32, _d, _d, _d, _d, _d, _i32, _i32, _p, _p, _p, _p, _d, _d, _i32, _i32, _p, _p, _p,
          _p, _u64, _u64, _p],
+    ),
+    "ebm_ghmc_adapt_chain_mass_f32": (  # ... with `mass_kind, mass_scalar, mass_diag` behind `temperature`
+        C.c_int,
+        [_ENERGY_P, _p, _p, _i64, _i32, _i32, _i32, _d, _d, _d, _d, _d, _i32, _i32, _p, _p, _p, _p, _d, _d, _i32, _d, _p, _i32, _i32,
+         _p, _p, _p, _p, _u64, _u64, _p],
     ),
     "ebm_kinetic_moments_f32": (
         C.c_int,

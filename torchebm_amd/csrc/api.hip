@@ -8,6 +8,7 @@
 #include "chain_launch.h"
 #include "../../include/ebm_hip_mass_mlp.h"  // the two massed MLP walks' declarations (a companion of ebm_hip.h)
 #include "ghmc_adapt_launch.h"               // the adapting generalized-HMC entry (its companion header: ebm_hip_adapt.h)
+#include "ghmc_adapt_mass_launch.h"          // ... with a mass (its companion header: ebm_hip_adapt_mass.h)
 
 namespace ebm {
 
@@ -846,6 +847,33 @@ int ebm_ghmc_adapt_chain_f32(const ebm_energy_t* energy, float* x, float* v, int
   if (!aligned16(v) || (traj && !aligned16(traj)) || (noise && !aligned16(noise)))
     return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
   return ghmc_adapt_chain_launch(q, (hipStream_t)stream);
+}
+
+// (the checks of ebm_ghmc_adapt_chain_f32 in its order, then the mass, all in front of the empty call)
+int ebm_ghmc_adapt_chain_mass_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t n_mh,
+                                  int32_t n_leapfrog, double eps0, double target_accept, double mu, double eps_min, double eps_max,
+                                  int32_t n_adapt, int32_t init_da, float* da, const float* da_table, float* eps_trace,
+                                  float* alpha_mean, double gamma, double temperature, int32_t mass_kind, double mass_scalar,
+                                  const float* mass_diag, int32_t draw_v0, int32_t thin, float* traj, uint8_t* accept_mask,
+                                  const float* noise, const float* u, uint64_t seed, uint64_t offset, void* stream) {
+  const char* who = "ebm_ghmc_adapt_chain_mass_f32";
+  if (energy && energy->kind == EBM_ENERGY_MLP)
+    return fail(EBM_EKIND, "%s: the MLP energy has no generalized-HMC kernel (the sampler's eager route takes it)", who);
+  if (int r = check_energy(energy, dim, who)) return r;
+  if (int r = ghmc_check_geometry(dim)) return r;
+  if (int r = check_state(x, n_chains, dim, who)) return r;
+  if (!v) return fail(EBM_EINVAL, "%s: velocity pointer is NULL", who);
+  if (int r = check_ghmc_parameters(n_mh, n_leapfrog, thin, eps0, gamma, temperature, who)) return r;
+  const GhmcAdaptChainReq q{*energy, x, v, n_chains, dim, n_mh, n_leapfrog, eps0, gamma, temperature, target_accept, mu, eps_min,
+                            eps_max, n_adapt, init_da, da, da_table, draw_v0 != 0, thin, traj, accept_mask, eps_trace, alpha_mean,
+                            noise, u, seed, offset};
+  if (int r = ghmc_adapt_check(q, who)) return r;
+  const ChainMass mass{mass_kind, mass_scalar, mass_diag};
+  if (int r = check_chain_mass(mass, who)) return r;
+  if (n_chains == 0) return 0;
+  if (!aligned16(v) || (traj && !aligned16(traj)) || (noise && !aligned16(noise)))
+    return fail(EBM_EINVAL, "%s: pointers must be 16-byte aligned", who);
+  return ghmc_adapt_mass_chain_launch(GhmcAdaptMassChainReq{q, mass}, (hipStream_t)stream);
 }
 
 // Both running-moments entries of the two walkers, as the underdamped pair; the analytic entry's geometry stands in front of its

@@ -9,7 +9,8 @@ from .kinetic import UnderdampedLangevin
 from .langevin import LangevinDynamics
 from .moments import ChainMoments, RunningMoments
 from .tempering import ReplicaExchangeHMC, ReplicaExchangeLangevin
+from .warmup import Warmup
 
 __all__ = ["LangevinDynamics", "HamiltonianMonteCarlo", "GradientDescentSampler", "NesterovSampler",
            "ReplicaExchangeLangevin", "ReplicaExchangeHMC", "AnnealedImportanceSampling", "AISResult", "ChainMoments", "RunningMoments",
-           "UnderdampedLangevin", "GeneralizedHMC", "StepSizeAdaptation"]
+           "UnderdampedLangevin", "GeneralizedHMC", "StepSizeAdaptation", "Warmup"]

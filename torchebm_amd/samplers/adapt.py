@@ -20,7 +20,11 @@ Two routes, chosen once per call (``adapt_route``):
            no ``model_kwargs`` (and, for ``HamiltonianMonteCarlo``, the plain leapfrog integrator): the whole call is ONE launch of
            ``ebm_ghmc_adapt_chain_f32`` (include/ebm_hip_adapt.h states the recurrence exactly; docs/design/adapt.md the
            kernel).  ``HamiltonianMonteCarlo`` calls the same entry with ``gamma = inf``, ``T = 1``.
-``eager``  everything else (the CPU, an ``nn.Module`` or ``MLPEnergy``, a mass, a scheduler, wider rows): the same recurrence in
+``fused_mass``  a sampler built with ``mass=`` under the conditions of ``fused``, and ONLY with the opt-in
+           ``sampler.fused_adapt_mass = True``: ONE launch of ``ebm_ghmc_adapt_chain_mass_f32`` (include/ebm_hip_adapt_mass.h;
+           docs/design/adapt_mass.md).  The carried plane is then the momentum ``p ~ N(0, T m)``; the mass arguments are
+           ``sample()``'s on its ``fused_mass`` route.  Off by default: a massed sampler keeps the eager route and its bits.
+``eager``  everything else (the CPU, an ``nn.Module`` or ``MLPEnergy``, a mass without the opt-in, a scheduler, wider rows): the same recurrence in
            torch ops around the safe-mode leapfrog transition of the samplers' eager routes, drawing in ``GeneralizedHMC``'s
            documented order: ``randn(n, dim)`` for the start velocities (only when none are passed), then ``randn(n, dim)`` and
            ``rand(n)`` per transition.
@@ -38,9 +42,11 @@ import torch
 
 from .. import _lib, _rng
 from ..core.energies import fused_spec_for
+from ..integrators.symplectic import _mass_args
 from ._chain_host import mass_forms, mass_row
 
 ENTRY = "ebm_ghmc_adapt_chain_f32"
+ENTRY_MASS = "ebm_ghmc_adapt_chain_mass_f32"
 FUSED_MAX_DIM = 256  # one vector per lane (csrc/ghmc_adapt.hip)
 
 
@@ -87,15 +93,19 @@ def _f32(value: float) -> float:
 
 
 def adapt_route(sampler, x: torch.Tensor, friction: float, model_kwargs=None):
-    """``("fused", spec)`` or ``("eager", None)``: the sampler's own routing, narrowed to what the adapting kernel takes."""
+    """``("fused", spec)``, ``("fused_mass", spec)`` or ``("eager", None)``: the sampler's own routing, narrowed to what the
+    adapting kernels take.  A massed sampler is fused only with its opt-in ``fused_adapt_mass``."""
     route, spec = sampler._route(x, model_kwargs or {})
-    if route != "fused" or spec is None or getattr(sampler, "mass", None) is not None:
+    massed = getattr(sampler, "mass", None) is not None
+    if route not in ("fused", "fused_mass") or spec is None:  # (GeneralizedHMC names its massed route, HamiltonianMonteCarlo does not)
+        return "eager", None
+    if massed and not getattr(sampler, "fused_adapt_mass", False):
         return "eager", None
     if spec.kind == _lib.ENERGY_MLP or x.ndim != 2 or x.shape[1] > FUSED_MAX_DIM:
         return "eager", None
     if not sampler.schedulers["step_size"].is_constant():
         return "eager", None
-    return "fused", spec
+    return ("fused_mass" if massed else "fused"), spec
 
 
 def eager_adapt(sampler, x, v, n_adapt, n_steps, eps0, friction, temperature, n_leapfrog, target_accept, mu, bounds, table,
@@ -178,7 +188,8 @@ def eager_adapt(sampler, x, v, n_adapt, n_steps, eps0, friction, temperature, n_
 
 def fused_adapt(sampler, spec, x, v, n_adapt, n_steps, eps0, friction, temperature, n_leapfrog, target_accept, mu, bounds, table,
                 generator):
-    """ONE launch of ``ebm_ghmc_adapt_chain_f32`` -> ``(x, v, da [3, n], alpha_mean [n])``; never the caller's tensors."""
+    """ONE launch of ``ebm_ghmc_adapt_chain_f32`` -- of ``ebm_ghmc_adapt_chain_mass_f32`` for a sampler with a mass -- ->
+    ``(x, v, da [3, n], alpha_mean [n])``; never the caller's tensors."""
     n, dim = x.shape
     state = _lib.dense_f32(x).clone()  # the kernel updates in place
     draw_v0 = v is None
@@ -188,12 +199,16 @@ def fused_adapt(sampler, spec, x, v, n_adapt, n_steps, eps0, friction, temperatu
     table_d = table.to(x.device, non_blocking=True)
     seed, step0 = _rng.reserve(generator, x.device, 2 * n_steps + 1)
     stream = _lib.stream_handle(x.device)
+    entry, mass = ENTRY, ()
+    if getattr(sampler, "mass", None) is not None:  # (kind, scalar, pointer) directly behind `temperature`, as sample() passes them
+        kind, m_scalar, m_diag = _mass_args(sampler.mass, state)
+        entry, mass = ENTRY_MASS, (kind, m_scalar, _lib.ptr(m_diag))
     if n > 0 and n_steps > 0:
         _lib.call(
-            ENTRY,
+            entry,
             spec.to_c(), _lib.ptr(state), _lib.ptr(vel), n, dim, n_steps, n_leapfrog, eps0, target_accept, mu, bounds[0], bounds[1],
-            n_adapt, _lib.DA_INIT, _lib.ptr(da), _lib.ptr(table_d), None, _lib.ptr(alpha_mean), friction, temperature, int(draw_v0),
-            1, None, None, None, None, seed, step0, stream,
+            n_adapt, _lib.DA_INIT, _lib.ptr(da), _lib.ptr(table_d), None, _lib.ptr(alpha_mean), friction, temperature, *mass,
+            int(draw_v0), 1, None, None, None, None, seed, step0, stream,
         )
     return state, vel, da, alpha_mean
 
@@ -227,7 +242,7 @@ def adapt_step_size(sampler, friction: float, temperature: float, x=None, dim=No
         table = da_table(n_steps, 0, t0, gamma, kappa)
         route, spec = adapt_route(sampler, x, friction)
         n_leapfrog = int(sampler.n_leapfrog_steps)
-        run = (lambda *a: fused_adapt(sampler, spec, *a)) if route == "fused" else (lambda *a: eager_adapt(sampler, *a))
+        run = (lambda *a: fused_adapt(sampler, spec, *a)) if route != "eager" else (lambda *a: eager_adapt(sampler, *a))
         state, vel, da, alpha_mean = run(x, velocity, n_steps, n_steps, eps0, friction, temperature, n_leapfrog, target_accept, mu,
                                          (lo, hi), table, generator)
         result = StepSizeAdaptation(state, vel, da[0], alpha_mean, pool_step_sizes(da[0]), da)

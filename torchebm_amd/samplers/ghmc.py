@@ -100,6 +100,10 @@ class GeneralizedHMC(BaseSampler):
     #: is ONE launch of ``ebm_ghmc_mlp_chain_mass_f32`` (docs/design/mass_mlp.md).  Off by default: with ``fused_mlp`` alone a
     #: massed sampler on an ``MLPEnergy`` keeps the eager route and its bits.
     fused_mlp_mass = False
+    #: opt-in read by ``adapt_step_size`` of a sampler built with ``mass=``: an eligible call (the conditions of ``fused_mass``) is
+    #: ONE launch of ``ebm_ghmc_adapt_chain_mass_f32`` (docs/design/adapt_mass.md).  Off by default: a massed sampler's
+    #: ``adapt_step_size`` keeps the eager route and its bits.  (``warmup()`` is new and takes the launch without it.)
+    fused_adapt_mass = False
 
     def __init__(
         self,
@@ -264,12 +268,35 @@ class GeneralizedHMC(BaseSampler):
         ``apply=False`` reads nothing back.  A production run at the adapted step accepts somewhat MORE than ``target_accept``
         (the averaged iterate is not the last one).  On the fused route (module docstring of ``samplers/adapt.py``) the call is
         ONE launch of ``ebm_ghmc_adapt_chain_f32``; a mass, a scheduler, the MLP energy, wider rows and the CPU run the same
-        recurrence in torch ops.  The caller's ``x`` and ``velocity`` are never written.
+        recurrence in torch ops.  With the opt-in ``fused_adapt_mass`` a sampler with a mass is ONE launch too, of
+        ``ebm_ghmc_adapt_chain_mass_f32`` (``velocity`` is then the momentum plane).  The caller's ``x`` and ``velocity`` are
+        never written.
         """
         from .adapt import adapt_step_size
 
         return adapt_step_size(self, self.friction, self.temperature, x, dim, n_steps, n_samples, target_accept, init_step_size, t0,
                                gamma, kappa, mu_factor, bounds, velocity, generator, apply)
+
+    def warmup(self, x=None, dim=None, n_samples=1, windows=(50, 50, 100), final_steps=50, target_accept=0.8, regularize=True,
+               generator=None, apply=True, **dual_averaging_constants):
+        """Stan's warm-up in windows (``samplers/warmup.py``): for each ``w`` in ``windows`` adapt the step size for ``w``
+        transitions under the current mass (``adapt_step_size``, fresh momenta, starting from the previous window's pooled step
+        size), then set the diagonal mass to ``1 / var`` of the window's final positions pooled over ALL CHAINS (with
+        ``regularize`` shrunk as Stan shrinks it: ``var <- N/(N+5) var + 1e-3 * 5/(N+5)``; a coordinate whose variance is not
+        finite and positive keeps its mass); then one terminal window of ``final_steps`` under the final mass.  Returns a
+        :class:`Warmup` (``x``, ``step_size``, ``mass`` and the per-window lists).  ``apply=True`` sets the sampler's step size and
+        its mass as the constructor would; ``apply=False`` leaves the sampler as it was.  Under the conditions of the fused routes
+        every window is ONE launch -- ``warmup()`` treats the massed route as eligible without the opt-in ``fused_adapt_mass`` --
+        and costs ONE host read, the pooled step size.  ``**dual_averaging_constants``: ``t0``, ``gamma``, ``kappa``,
+        ``mu_factor``, ``bounds`` of ``adapt_step_size``.
+
+        Raises:
+            ValueError: fewer than 2 rows (the variance is an ensemble estimate across chains), or what ``adapt_step_size`` refuses.
+        """
+        from .warmup import warmup
+
+        return warmup(self, x, dim, n_samples, windows, final_steps, target_accept, regularize, generator, apply,
+                      **dual_averaging_constants)
 
     # ---------------------------------------------------------------------------------
     # route: torch ops

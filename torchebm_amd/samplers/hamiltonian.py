@@ -65,6 +65,12 @@ class HamiltonianMonteCarlo(BaseSampler):
     #: arithmetic between the draws.)
     exact: bool = False
 
+    #: opt-in read by ``adapt_step_size`` of a sampler built with ``mass=``: an eligible call (CUDA fp32, an analytic energy,
+    #: ``dim <= 256``, a constant step size, the plain leapfrog integrator) is ONE launch of ``ebm_ghmc_adapt_chain_mass_f32``
+    #: (docs/design/adapt_mass.md).  Off by default: a massed sampler's ``adapt_step_size`` keeps the eager route and its bits.
+    #: (``warmup()`` is new and takes the launch without it.)
+    fused_adapt_mass = False
+
     #: energies the literal kernel (``ebm_hmc_chain_audit_f32``) takes, and its widest state
     _EXACT_KINDS = (_lib.ENERGY_DOUBLE_WELL, _lib.ENERGY_HARMONIC)
     _EXACT_MAX_DIM = 256
@@ -243,7 +249,8 @@ class HamiltonianMonteCarlo(BaseSampler):
         the sampler's.  On the fused route (CUDA fp32, an analytic energy, ``dim <= 256``, ``mass is None``, a constant step size,
         the plain leapfrog integrator) the call is ONE launch of ``ebm_ghmc_adapt_chain_f32`` with ``gamma = inf``; anything else
         runs the recurrence in torch ops with the safe-mode leapfrog step, drawing ``randn(n, dim)`` for the (discarded) start
-        velocities when none are passed, then ``randn(n, dim)`` and ``rand(n)`` per transition.
+        velocities when none are passed, then ``randn(n, dim)`` and ``rand(n)`` per transition.  With the opt-in
+        ``fused_adapt_mass`` a sampler with a mass is ONE launch too, of ``ebm_ghmc_adapt_chain_mass_f32``.
 
         Raises:
             ValueError: a symplectic integrator other than the plain leapfrog (the recurrence spells that step), or what
@@ -255,6 +262,28 @@ class HamiltonianMonteCarlo(BaseSampler):
             raise ValueError("adapt_step_size needs the plain leapfrog integrator")
         return adapt_step_size(self, math.inf, 1.0, x, dim, n_steps, n_samples, target_accept, init_step_size, t0, gamma, kappa,
                                mu_factor, bounds, velocity, generator, apply)
+
+    def warmup(self, x=None, dim=None, n_samples=1, windows=(50, 50, 100), final_steps=50, target_accept=0.8, regularize=True,
+               generator=None, apply=True, **dual_averaging_constants):
+        """Stan's warm-up in windows (``samplers/warmup.py``): for each ``w`` in ``windows`` adapt the step size for ``w``
+        transitions under the current mass (``adapt_step_size``, fresh momenta, starting from the previous window's pooled step
+        size), then set the diagonal mass to ``1 / var`` of the window's final positions pooled over ALL CHAINS (with
+        ``regularize`` shrunk as Stan shrinks it: ``var <- N/(N+5) var + 1e-3 * 5/(N+5)``; a coordinate whose variance is not
+        finite and positive keeps its mass); then one terminal window of ``final_steps`` under the final mass.  Returns a
+        :class:`Warmup` (``x``, ``step_size``, ``mass`` and the per-window lists).  ``apply=True`` sets the sampler's step size and
+        its mass as the constructor would; ``apply=False`` leaves the sampler as it was.  Under the conditions of the fused routes
+        every window is ONE launch -- ``warmup()`` treats the massed route as eligible without the opt-in ``fused_adapt_mass`` --
+        and costs ONE host read, the pooled step size.  ``**dual_averaging_constants``: ``t0``, ``gamma``, ``kappa``,
+        ``mu_factor``, ``bounds`` of ``adapt_step_size``.
+
+        Raises:
+            ValueError: fewer than 2 rows (the variance is an ensemble estimate across chains), a symplectic integrator other than the plain leapfrog, or what
+                ``adapt_step_size`` refuses.
+        """
+        from .warmup import warmup
+
+        return warmup(self, x, dim, n_samples, windows, final_steps, target_accept, regularize, generator, apply,
+                      **dual_averaging_constants)
 
     # ---------------------------------------------------------------------------------
     # route: per-transition loop
