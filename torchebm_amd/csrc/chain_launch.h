@@ -264,7 +264,7 @@ inline void fill_scalar_mass(Args& a, double m) {
   a.mass_safe = (float)(m < 1e-10 ? 1e-10 : m);
 }
 
-// The mass of the massed kinetic walkers (KineticMassArgs, GhmcMassArgs): the kind, the scalar forms, the diagonal's pointer.
+// The mass of the massed kinetic walkers (KineticMassArgs, GhmcMassArgs, ghmc::Mass): the kind, the scalar forms, the diagonal's pointer.
 template <class Args>
 inline void fill_mass(Args& a, const ChainMass& m) {
   a.mass_kind = m.kind;

@@ -1,5 +1,5 @@
 // The request of ebm_ghmc_adapt_chain_f32 (include/ebm_hip_adapt.h) and its launcher's declarations: what api.hip hands to
-// ghmc_adapt.hip.  A header of its own beside chain_launch.h, which every kernel unit includes.
+// ghmc.hip.  A header of its own beside chain_launch.h, which every kernel unit includes.
 #pragma once
 #include "chain_launch.h"
 #include "../../include/ebm_hip_adapt.h"  // the entry's declaration and EBM_DA_* (a companion of ebm_hip.h)

@@ -1,5 +1,5 @@
-// The generalized-HMC kernels of ONE energy kind (ghmc_kernel.h).  The Makefile compiles this source once per kind
-// (-DEBM_UNIT_KIND=...) into ghmc_<kind>.o, so that the kinds build in parallel.
+// The generalized-HMC kernels of ONE energy kind (ghmc_kernel.h: unit mass, fixed step).  The Makefile compiles this source once
+// per kind (-DEBM_UNIT_KIND=...) into ghmc_<kind>.o, so that the kinds build in parallel.
 #include "ghmc_kernel.h"
 
 namespace ebm {

@@ -216,7 +216,8 @@ __device__ __forceinline__ bool metropolis_accept(float dH, float uu, bool init,
 }
 
 // ---- a scalar or diagonal mass, shared by hmc_chain_body and the massed kinetic walkers (kinetic_mass_kernel.h,
-//      ghmc_mass_kernel.h).  Args carries mass_raw, mass_sqrt, mass_safe (the scalar forms) and mass_diag.
+//      ghmc_mass_kernel.h, the massed walk of ghmc_kernel.h).  Args carries mass_raw, mass_sqrt, mass_safe (the scalar forms)
+//      and mass_diag.
 
 // The mass forms per slot: raw (kinetic energy), sqrt (momentum draw), clamped (drift).  A slot that holds no column gets 1.
 template <class LaneT, class Args>

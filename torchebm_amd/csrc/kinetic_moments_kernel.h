@@ -9,9 +9,10 @@
 // needs; recip[c - 1], the burn-in test and the half switch are wave-uniform, and the half switch is taken once per launch
 // (next_half_*), not selected per step.
 //
-// Transitions: kinetic_chain's recurrence and ghmc_chain's transition, operation for operation; what is counted is the state
-// behind the transition.  BAOAB with energies takes E of the post-step position out of the one evaluation inside the step
-// (eval<true>): that position is the counted state, so nothing is pending and nothing is evaluated behind the loop.
+// Transitions: kinetic_chain's recurrence and the transition of ghmc_kernel.h's walk (unit mass, fixed step), operation for
+// operation; what is counted is the state behind the transition.  BAOAB with energies takes E of the post-step position out
+// of the one evaluation inside the step (eval<true>): that position is the counted state, so nothing is pending and nothing is
+// evaluated behind the loop.
 #pragma once
 #include "moments_kernel.h"
 
@@ -159,7 +160,8 @@ __global__ __launch_bounds__(kBlock) void moments_kinetic_chain_energy(KineticMo
   baoab_body<KIND, G, FULL, true>(a);
 }
 
-// ---- GHMC: ghmc_chain's transition; the energy of a counted state is the one the transition carries.
+// ---- GHMC: the transition of ghmc_kernel.h's walk (unit mass, fixed step); the energy of a counted state is the one the
+//      transition carries.
 template <int KIND, int G, int NV, bool FULL>
 __global__ __launch_bounds__(kBlock) void moments_ghmc_chain(KineticMomentsArgs a) {
   static_assert(NV == 1, "one vector per lane");

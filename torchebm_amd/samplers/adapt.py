@@ -47,7 +47,7 @@ from ._chain_host import mass_forms, mass_row
 
 ENTRY = "ebm_ghmc_adapt_chain_f32"
 ENTRY_MASS = "ebm_ghmc_adapt_chain_mass_f32"
-FUSED_MAX_DIM = 256  # one vector per lane (csrc/ghmc_adapt.hip)
+FUSED_MAX_DIM = 256  # one vector per lane (csrc/ghmc.hip)
 
 
 def da_table(n_adapt: int, m0: int = 0, t0: float = 10.0, gamma: float = 0.05, kappa: float = 0.75) -> torch.Tensor:
