@@ -16,6 +16,7 @@ from .core import (  # noqa: F401
     GaussianModel,
     HarmonicModel,
     MLPEnergy,
+    MLP3Energy,
 )
 from .integrators import EulerMaruyamaIntegrator, LeapfrogIntegrator  # noqa: F401
 from .losses import ContrastiveDivergence, EnergyMatchingContrastive  # noqa: F401

@@ -25,6 +25,7 @@ from .energies import (
     RosenbrockModel,
     ring_mixture,
 )
+from .mlp3 import MLP3Energy
 from .integrator_base import BaseIntegrator, BaseSDERungeKuttaIntegrator, BaseSymplecticIntegrator
 from .sampler_base import BaseSampler
 from .loss_base import BaseContrastiveDivergence, BaseLoss
@@ -34,7 +35,7 @@ __all__ = [
     "BaseScheduler", "ConstantScheduler", "ExponentialDecayScheduler", "LinearScheduler",
     "CosineScheduler", "MultiStepScheduler", "WarmupScheduler", "TemperatureScheduler", "Schedulable",
     "BaseModel", "DoubleWellModel", "GaussianModel", "HarmonicModel", "GaussianMixtureModel",
-    "RosenbrockModel", "AckleyModel", "RastriginModel", "FusedSpec", "MLPEnergy", "ring_mixture",
+    "RosenbrockModel", "AckleyModel", "RastriginModel", "FusedSpec", "MLPEnergy", "MLP3Energy", "ring_mixture",
     "BaseIntegrator", "BaseSDERungeKuttaIntegrator", "BaseSymplecticIntegrator",
     "BaseSampler", "BaseLoss", "BaseContrastiveDivergence",
 ]

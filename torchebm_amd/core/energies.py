@@ -720,7 +720,8 @@ class MLPEnergy(BaseModel):
 FUSED_MAX_ROW = 1024
 
 
-def fused_spec_for(model, x: torch.Tensor, model_kwargs: Optional[dict], *, cap_elementwise: bool = True) -> Optional[FusedSpec]:
+def fused_spec_for(model, x: torch.Tensor, model_kwargs: Optional[dict], *, cap_elementwise: bool = True,
+                   mlp3: bool = False) -> Optional[FusedSpec]:
     """The descriptor the fused kernels need for sampling ``model`` on the state ``x`` -- or ``None`` when
     the configuration must take the per-step route (``model.gradient`` + update kernel):
 
@@ -734,14 +735,17 @@ def fused_spec_for(model, x: torch.Tensor, model_kwargs: Optional[dict], *, cap_
       for element-wise energies where the caller uses the flat kernel, which has no row limit);
     * a state that is not ``[n, dim]``: the analytic energies reduce over the last axis only, so for a
       ``[n, a, b]`` state the reference's ``BaseModel.gradient`` raises ``ValueError`` (energy shape
-      ``(n, a)`` is not ``(n,)``, core/base_model.py:95-99) -- and so does the step route here.
+      ``(n, a)`` is not ``(n,)``, core/base_model.py:95-99) -- and so does the step route here;
+    * an ``MLP3Energy`` (kind ``ENERGY_MLP3``), unless the caller says ``mlp3=True``: only its own two entries
+      (include/ebm_hip_mlp3.h) take that kind, so only their callers ask for it -- to every other sampler it is
+      "any other energy".
     """
     from .schedules import Schedulable
 
     if model_kwargs or not hasattr(model, "fused_spec") or isinstance(model, Schedulable):
         return None
     spec = model.fused_spec()
-    if spec is None:
+    if spec is None or (spec.kind == _lib.ENERGY_MLP3 and not mlp3):
         return None
     if x.ndim != 2:
         return None

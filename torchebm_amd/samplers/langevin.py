@@ -129,7 +129,7 @@ class LangevinDynamics(BaseSampler):
 
     def _fusable_spec(self, x: torch.Tensor, model_kwargs: Dict[str, Any]) -> Optional[FusedSpec]:
         # element-wise energies run on the flat kernel, which has no row-width limit
-        return fused_spec_for(self.model, x, model_kwargs, cap_elementwise=False)
+        return fused_spec_for(self.model, x, model_kwargs, cap_elementwise=False, mlp3=True)
 
     # ---------------------------------------------------------------------------------
     # public API
@@ -165,6 +165,14 @@ class LangevinDynamics(BaseSampler):
         x = self._init_state(x, dim, n_samples, generator)
         model_kwargs = self._prepare_model_kwargs(model_kwargs)
         route, spec = self._route(x, model_kwargs)
+        if route == "fused" and spec.kind == _lib.ENERGY_MLP3:
+            # the three-hidden-layer MLP has ONE chain kernel, the plain call's (ebm_langevin_chain_mlp3_f32); everything else
+            # is the step route, whose gradient is that energy's one-launch evaluation
+            plain = (thin == 1 and not return_trajectory and not return_diagnostics and self.clamp is None
+                     and self._graph_eligible(model_kwargs) and getattr(self, "_graph_coords", None) is None)
+            if plain:
+                return self._sample_mlp3(x, spec, n_steps, generator)
+            route, spec = "step", None
         if route == "fused":
             return self._sample_fused(x, spec, n_steps, thin, return_trajectory, return_diagnostics, generator)
         return self._sample_stepwise(
@@ -438,6 +446,23 @@ class LangevinDynamics(BaseSampler):
         self.advance_schedulers(n_steps)
         out = traj if want_traj else state
         return (out, diag) if want_diag else out
+
+    def _sample_mlp3(self, x, spec: FusedSpec, n_steps, generator):
+        """The plain call on an ``MLP3Energy``: all ``n_steps`` steps in ONE ``ebm_langevin_chain_mlp3_f32`` launch, which reads
+        the caller's tensor and writes a fresh one (the caller's own with ``donate_input``)."""
+        n, dim = x.shape
+        src = _lib.dense_f32(x)
+        seed, step0 = _rng.reserve(generator, x.device, n_steps)
+        if n_steps > 0 and n > 0:
+            donated = self.donate_input and src.data_ptr() == x.data_ptr()
+            state = src if donated else torch.empty_like(src, memory_format=torch.contiguous_format)
+            a, sq, coef = em_coefficients(self.get_scheduled_value("step_size"), self.get_scheduled_value("noise_scale"))
+            _lib.call("ebm_langevin_chain_mlp3_f32", spec.to_c(), _lib.ptr(src), _lib.ptr(state), n, dim, n_steps, a, sq, coef,
+                      None, seed, step0, _lib.stream_handle(x.device))
+        else:
+            state = src if self.donate_input else src.clone()
+        self.advance_schedulers(n_steps)
+        return state
 
     def _launcher(self, spec_c, state, rows, thin, seed, step0, stream, src):
         """``launch(t0, steps, traj_piece, records, first)`` of the drivers of a call with diagnostics: steps
