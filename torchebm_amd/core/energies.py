@@ -736,13 +736,15 @@ def fused_spec_for(model, x: torch.Tensor, model_kwargs: Optional[dict], *, cap_
     * a state that is not ``[n, dim]``: the analytic energies reduce over the last axis only, so for a
       ``[n, a, b]`` state the reference's ``BaseModel.gradient`` raises ``ValueError`` (energy shape
       ``(n, a)`` is not ``(n,)``, core/base_model.py:95-99) -- and so does the step route here;
-    * an ``MLP3Energy`` (kind ``ENERGY_MLP3``), unless the caller says ``mlp3=True``: only its own two entries
-      (include/ebm_hip_mlp3.h) take that kind, so only their callers ask for it -- to every other sampler it is
-      "any other energy".
+    * an ``MLP3Energy`` (kind ``ENERGY_MLP3``), unless the caller says ``mlp3=True``: only its own entries
+      (include/ebm_hip_mlp3.h and ebm_hip_mlp3_stream.h) take that kind, so only their callers ask for it -- to every
+      other sampler it is "any other energy", and its spec (which may build a weight image) is not even formed.
     """
     from .schedules import Schedulable
 
     if model_kwargs or not hasattr(model, "fused_spec") or isinstance(model, Schedulable):
+        return None
+    if getattr(model, "FUSED_SPEC_ON_REQUEST", False) and not mlp3:
         return None
     spec = model.fused_spec()
     if spec is None or (spec.kind == _lib.ENERGY_MLP3 and not mlp3):

@@ -37,12 +37,23 @@ class MLP3Energy(BaseModel):
       step size and noise scale, no clamp, trajectory or diagnostics, ``thin == 1``, no ``model_kwargs``); any other
       configuration takes the per-step route.
 
+    At ``hidden == 128`` and ``33 <= in_dim <= 128`` both go through the streamed bf16 kernel instead
+    (``ebm_energy_grad_mlp3_stream_f32`` / ``ebm_langevin_chain_mlp3_stream_f32``, include/ebm_hip_mlp3_stream.h,
+    docs/design/mlp3_stream.md), whose spec carries a pre-split weight image in ``aux``; ``streamed_bf16 = True`` opts
+    ``in_dim <= 32`` into that kernel as well.
+
     The parameters are ordinary ``nn.Linear`` weights, re-read (packed) at every call.
     """
 
     HIP_GRADIENT = True
+    #: ``fused_spec_for`` forms this energy's spec only for a caller that asks for its kind (``mlp3=True``)
+    FUSED_SPEC_ON_REQUEST = True
     #: hidden width -> widest input with a kernel (csrc/mlp3.hip: what is resident in LDS at each width)
     FUSED_MAX_DIM = {64: 128, 128: 32}
+    #: hidden width -> widest input of the streamed bf16 kernel (csrc/mlp3_stream.hip), the only kernel above FUSED_MAX_DIM
+    STREAMED_MAX_DIM = {128: 128}
+    #: take the streamed bf16 kernel also where the exact-f32 kernel of FUSED_MAX_DIM serves (hidden 128, in_dim <= 32)
+    streamed_bf16 = False
     ROWS_INDEPENDENT = True
 
     def __init__(self, in_dim: int = 2, hidden: int = 128, *args, **kwargs):
@@ -94,7 +105,9 @@ class MLP3Energy(BaseModel):
                        for m in mods)
 
     def fused_spec(self) -> Optional[FusedSpec]:
-        if not self._is_exactly(MLP3Energy) or self.in_dim < 1 or self.in_dim > self.FUSED_MAX_DIM.get(self.hidden, 0):
+        resident = 1 <= self.in_dim <= self.FUSED_MAX_DIM.get(self.hidden, 0)
+        streamed = 1 <= self.in_dim <= self.STREAMED_MAX_DIM.get(self.hidden, 0) and (self.streamed_bf16 or not resident)
+        if not self._is_exactly(MLP3Energy) or not (resident or streamed):
             return None
         if not self._plain_net():
             return None
@@ -103,11 +116,19 @@ class MLP3Energy(BaseModel):
             return None
         with torch.no_grad():  # W1[H,d] b1[H] W2[H,H] b2[H] W3[H,H] b3[H] w4[H] b4[1], packed on every call: the weights train
             packed = torch.cat([p.detach().reshape(-1) for p in params])
-        return FusedSpec(_lib.ENERGY_MLP3, n_comp=int(self.hidden), dev0=packed, langevin_only=True, dim=int(self.in_dim), hmc=False)
+            image = None
+            if streamed:  # the pre-split image of W1 and W3 the streamed kernel walks: rebuilt with `packed`, i.e. on every call
+                n_img = int(_lib.lib().ebm_mlp3_image_bytes(int(self.hidden), int(self.in_dim)))
+                image = torch.empty(n_img // 4, dtype=torch.int32, device=packed.device)
+                _lib.call("ebm_mlp3_image_f32", packed.data_ptr(), int(self.hidden), int(self.in_dim), image.data_ptr(),
+                          _lib.stream_handle(packed.device))
+        return FusedSpec(_lib.ENERGY_MLP3, n_comp=int(self.hidden), dev0=packed, aux=image, langevin_only=True, dim=int(self.in_dim),
+                         hmc=False)
 
     def _hip_gradient(self, x: torch.Tensor, model_kwargs: Optional[dict]) -> Optional[torch.Tensor]:
-        """``gradient()`` in one ``ebm_energy_grad_mlp3_f32`` launch under the conditions ``MLPEnergy.gradient`` uses (fp32
-        ``[n, dim]`` CUDA state, no kwargs, no autocast); ``None`` sends the caller to autograd."""
+        """``gradient()`` in one ``ebm_energy_grad_mlp3_f32`` launch (``ebm_energy_grad_mlp3_stream_f32`` when the spec carries an
+        image) under the conditions ``MLPEnergy.gradient`` uses (fp32 ``[n, dim]`` CUDA state, no kwargs, no autocast); ``None``
+        sends the caller to autograd."""
         if model_kwargs or not x.is_cuda or x.dtype != torch.float32 or x.ndim != 2:
             return None
         if torch.is_autocast_enabled() or getattr(self, "use_mixed_precision", False):
@@ -119,6 +140,7 @@ class MLP3Energy(BaseModel):
         if state.data_ptr() % 16 != 0 or state.shape[0] == 0:
             return None
         grad = torch.empty_like(state)
-        _lib.call("ebm_energy_grad_mlp3_f32", spec.to_c(), state.data_ptr(), state.shape[0], state.shape[1], None, grad.data_ptr(),
+        entry = "ebm_energy_grad_mlp3_f32" if spec.aux is None else "ebm_energy_grad_mlp3_stream_f32"
+        _lib.call(entry, spec.to_c(), state.data_ptr(), state.shape[0], state.shape[1], None, grad.data_ptr(),
                   _lib.stream_handle(state.device))
         return grad

@@ -166,7 +166,8 @@ class LangevinDynamics(BaseSampler):
         model_kwargs = self._prepare_model_kwargs(model_kwargs)
         route, spec = self._route(x, model_kwargs)
         if route == "fused" and spec.kind == _lib.ENERGY_MLP3:
-            # the three-hidden-layer MLP has ONE chain kernel, the plain call's (ebm_langevin_chain_mlp3_f32); everything else
+            # the three-hidden-layer MLP has chain kernels for the plain call only (ebm_langevin_chain_mlp3_f32, or
+            # ebm_langevin_chain_mlp3_stream_f32 where the spec carries an image); everything else
             # is the step route, whose gradient is that energy's one-launch evaluation
             plain = (thin == 1 and not return_trajectory and not return_diagnostics and self.clamp is None
                      and self._graph_eligible(model_kwargs) and getattr(self, "_graph_coords", None) is None)
@@ -448,7 +449,7 @@ class LangevinDynamics(BaseSampler):
         return (out, diag) if want_diag else out
 
     def _sample_mlp3(self, x, spec: FusedSpec, n_steps, generator):
-        """The plain call on an ``MLP3Energy``: all ``n_steps`` steps in ONE ``ebm_langevin_chain_mlp3_f32`` launch, which reads
+        """The plain call on an ``MLP3Energy``: all ``n_steps`` steps in ONE ``ebm_langevin_chain_mlp3[_stream]_f32`` launch, which reads
         the caller's tensor and writes a fresh one (the caller's own with ``donate_input``)."""
         n, dim = x.shape
         src = _lib.dense_f32(x)
@@ -457,7 +458,9 @@ class LangevinDynamics(BaseSampler):
             donated = self.donate_input and src.data_ptr() == x.data_ptr()
             state = src if donated else torch.empty_like(src, memory_format=torch.contiguous_format)
             a, sq, coef = em_coefficients(self.get_scheduled_value("step_size"), self.get_scheduled_value("noise_scale"))
-            _lib.call("ebm_langevin_chain_mlp3_f32", spec.to_c(), _lib.ptr(src), _lib.ptr(state), n, dim, n_steps, a, sq, coef,
+            # (a spec with an image is the streamed bf16 kernel's: hidden width 128, include/ebm_hip_mlp3_stream.h)
+            entry = "ebm_langevin_chain_mlp3_f32" if spec.aux is None else "ebm_langevin_chain_mlp3_stream_f32"
+            _lib.call(entry, spec.to_c(), _lib.ptr(src), _lib.ptr(state), n, dim, n_steps, a, sq, coef,
                       None, seed, step0, _lib.stream_handle(x.device))
         else:
             state = src if self.donate_input else src.clone()
