@@ -35,7 +35,10 @@ class MLP3Energy(BaseModel):
       matrix cores), so every sampler's per-step route takes it;
     * ``LangevinDynamics.sample()`` is one launch of ``ebm_langevin_chain_mlp3_f32`` for the plain call (Euler-Maruyama, constant
       step size and noise scale, no clamp, trajectory or diagnostics, ``thin == 1``, no ``model_kwargs``); any other
-      configuration takes the per-step route.
+      configuration takes the per-step route;
+    * at ``hidden == 64``, ``HamiltonianMonteCarlo.sample()`` is one launch of ``ebm_hmc_chain_mlp3_f32``
+      (include/ebm_hip_mlp3_hmc.h, docs/design/mlp3_hmc.md) with no mass or a scalar one, ``exact`` off and no diagnostics;
+      ``thin``, ``return_trajectory`` and a scheduled step size stay in that launch.
 
     At ``hidden == 128`` and ``33 <= in_dim <= 128`` both go through the streamed bf16 kernel instead
     (``ebm_energy_grad_mlp3_stream_f32`` / ``ebm_langevin_chain_mlp3_stream_f32``, include/ebm_hip_mlp3_stream.h,
@@ -52,6 +55,8 @@ class MLP3Energy(BaseModel):
     FUSED_MAX_DIM = {64: 128, 128: 32}
     #: hidden width -> widest input of the streamed bf16 kernel (csrc/mlp3_stream.hip), the only kernel above FUSED_MAX_DIM
     STREAMED_MAX_DIM = {128: 128}
+    #: hidden width -> widest input of the HMC transition kernel (csrc/mlp3_hmc.hip; docs/design/mlp3_hmc.md: every width measured)
+    HMC_MAX_DIM = {64: 128}
     #: take the streamed bf16 kernel also where the exact-f32 kernel of FUSED_MAX_DIM serves (hidden 128, in_dim <= 32)
     streamed_bf16 = False
     ROWS_INDEPENDENT = True
@@ -123,7 +128,7 @@ class MLP3Energy(BaseModel):
                 _lib.call("ebm_mlp3_image_f32", packed.data_ptr(), int(self.hidden), int(self.in_dim), image.data_ptr(),
                           _lib.stream_handle(packed.device))
         return FusedSpec(_lib.ENERGY_MLP3, n_comp=int(self.hidden), dev0=packed, aux=image, langevin_only=True, dim=int(self.in_dim),
-                         hmc=False)
+                         hmc=image is None and self.in_dim <= self.HMC_MAX_DIM.get(self.hidden, 0))
 
     def _hip_gradient(self, x: torch.Tensor, model_kwargs: Optional[dict]) -> Optional[torch.Tensor]:
         """``gradient()`` in one ``ebm_energy_grad_mlp3_f32`` launch (``ebm_energy_grad_mlp3_stream_f32`` when the spec carries an

@@ -6,6 +6,7 @@
 // and dE/dx comes out where the state lives.  Rows, noise, the update and the lane helpers are mlp_wide_rows.h's; the matrix
 // operands are mlp_b16.h's (H = 64: three split bf16 images per matrix, all resident) or mlp_wide_body.h's contract<> on fp32
 // words (H = 128: two H x H split images do not fit LDS together, so this width runs the exact-f32 matrix instruction).
+// The set-up (parameters, LDS carve-up, staging, lane geometry) is mlp3_setup.inc, shared with mlp3_hmc_body.h.
 // The evaluation is text of its own, mlp3_eval.inc: six contractions and five epilogues, in order, nothing hidden behind
 // anything.  Two translation units instantiate the kernel: mlp3.hip (H = 64, DT 1 / 2 / 4) and mlp3_h128.hip (H = 128, DT 1).
 #pragma once
@@ -45,57 +46,7 @@ __global__ __launch_bounds__(kBlock, 1) void mlp3_chain(Args a) {
   constexpr int H = 32 * HT, DP = 32 * DT;
   constexpr int C1 = b16_cols(DT);        // B16: width of the W1 image
   constexpr int S1 = DP + 1, S2 = H + 1;  // fp32 words: the conflict-free row strides
-  const int dim = a.dim;
-  const float* W1g = a.params;
-  const float* b1g = W1g + H * dim;
-  const float* W2g = b1g + H;
-  const float* b2g = W2g + H * H;
-  const float* W3g = b2g + H;
-  const float* b3g = W3g + H * H;
-  const float* w4g = b3g + H;
-  const float b4 = w4g[H];
-  // ---- the LDS carve-up and the staging (once per launch)
-  float* const vecs = B16 ? wide_smem : wide_smem + 2 * H * S2 + H * S1;
-  float* const b1s = vecs;
-  float* const b2s = vecs + H;
-  float* const b3s = vecs + 2 * H;
-  float* const w4s = vecs + 3 * H;
-  [[maybe_unused]] float* const W2s = wide_smem;        // fp32 words
-  [[maybe_unused]] float* const W3s = W2s + H * S2;
-  [[maybe_unused]] float* const W1s = W3s + H * S2;     // columns >= dim zero
-  const mlpb16::lds_bytes img2 = (mlpb16::lds_bytes)(wide_smem + 4 * H);
-  const mlpb16::lds_bytes img3 = img2 + mlpb16::image_bytes(H, H);
-  const mlpb16::lds_bytes img1 = img3 + mlpb16::image_bytes(H, H);
-  if constexpr (B16) {
-    mlpb16::stage_image<H, H>(W2g, H, H, img2, kBlock);
-    mlpb16::stage_image<H, H>(W3g, H, H, img3, kBlock);
-    mlpb16::stage_image<H, C1>(W1g, H, dim, img1, kBlock);  // columns >= dim zero: the padding rows of dE/dx come out 0
-  } else {
-    for (int i = threadIdx.x; i < H * H; i += kBlock) {
-      W2s[(i / H) * S2 + (i % H)] = W2g[i];
-      W3s[(i / H) * S2 + (i % H)] = W3g[i];
-    }
-    for (int i = threadIdx.x; i < H * DP; i += kBlock) {
-      const int row = i / DP, c = i - row * DP;
-      W1s[row * S1 + c] = c < dim ? W1g[row * dim + c] : 0.0f;
-    }
-  }
-  for (int i = threadIdx.x; i < H; i += kBlock) {
-    b1s[i] = b1g[i];
-    b2s[i] = b2g[i];
-    b3s[i] = b3g[i];
-    w4s[i] = w4g[i];
-  }
-  __syncthreads();
-
-  const int lane = threadIdx.x & 63;
-  [[maybe_unused]] const mlpb16::Walk<H, C1> walk1(img1, B16 ? lane : 0);
-  [[maybe_unused]] const mlpb16::Walk<H, H> walk2(img2, B16 ? lane : 0);
-  [[maybe_unused]] const mlpb16::Walk<H, H> walk3(img3, B16 ? lane : 0);
-  const int m = lane & 31, h = lane >> 5;
-  const int64_t sample = ((int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * 32 + m;
-  const bool active = sample < a.n_chains;  // chains past n are neither loaded nor stored
-  const bool quads = (dim & 3) == 0;
+#include "mlp3_setup.inc"
   EBM_WIDE_LANES();
 
   // the state in the C/D layout: xr[td][r] = x[sample][32 td + row_of(r, h)], exactly zero beyond dim
@@ -137,17 +88,24 @@ __global__ __launch_bounds__(kBlock, 1) void mlp3_chain(Args a) {
   if (active) store_rows(lanes, a.x, sample, xr);
 }
 
-template <int HT, int DT>
-int launch(const Args& a, hipStream_t st, const char* who) {
+// One launch of KERNEL, a kernel of this energy at (HT, DT) that takes its arguments by value: the per-device LDS opt-in, one wave
+// per 32 chains.
+template <auto KERNEL, int HT, int DT, class KernelArgs>
+int launch_kernel(const KernelArgs& a, hipStream_t st, const char* who) {
   constexpr size_t smem = smem_bytes(HT, DT);
   static_assert(smem <= 160 * 1024, "the weights of this shape do not fit the CU's LDS");
   static DeviceOnce attr_once;  // the LDS opt-in is a per-device function attribute
   if (attr_once.first())        // > 64 KiB of dynamic LDS needs the opt-in
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(mlp3_chain<HT, DT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
   const int64_t blocks = ceil_div64(a.n_chains, 32 * (kBlock / 64));
   if (blocks > 0x7fffffffLL) return fail(EBM_EINVAL, "%s: too many chains for one launch", who);
-  hipLaunchKernelGGL((mlp3_chain<HT, DT>), dim3((unsigned)blocks), dim3(kBlock), smem, st, a);
+  hipLaunchKernelGGL(KERNEL, dim3((unsigned)blocks), dim3(kBlock), smem, st, a);
   return check_launch(who);
+}
+
+template <int HT, int DT>
+int launch(const Args& a, hipStream_t st, const char* who) {
+  return launch_kernel<&mlp3_chain<HT, DT>, HT, DT>(a, st, who);
 }
 
 int launch_h128(const Args& a, hipStream_t st, const char* who);  // mlp3_h128.hip

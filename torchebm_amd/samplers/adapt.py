@@ -101,7 +101,7 @@ def adapt_route(sampler, x: torch.Tensor, friction: float, model_kwargs=None):
         return "eager", None
     if massed and not getattr(sampler, "fused_adapt_mass", False):
         return "eager", None
-    if spec.kind == _lib.ENERGY_MLP or x.ndim != 2 or x.shape[1] > FUSED_MAX_DIM:
+    if spec.kind in (_lib.ENERGY_MLP, _lib.ENERGY_MLP3) or x.ndim != 2 or x.shape[1] > FUSED_MAX_DIM:
         return "eager", None
     if not sampler.schedulers["step_size"].is_constant():
         return "eager", None

@@ -155,9 +155,11 @@ class HamiltonianMonteCarlo(BaseSampler):
             torch.is_tensor(self.mass) and self.mass.ndim == 1 and self.mass.numel() == x.shape[-1]
         )
         if mass_ok:
-            spec = fused_spec_for(self.model, x, model_kwargs)
+            spec = fused_spec_for(self.model, x, model_kwargs, mlp3=True)
             if spec is not None and not spec.hmc:
                 spec = None  # (a wide MLP energy: fused for Langevin only)
+            if spec is not None and spec.kind == _lib.ENERGY_MLP3 and (torch.is_tensor(self.mass) or self.exact):
+                spec = None  # (ebm_hmc_chain_mlp3_f32: no diagonal mass, no literal body)
             if spec is not None and self.exact and not (spec.kind in self._EXACT_KINDS and x.shape[-1] <= self._EXACT_MAX_DIM):
                 spec = None  # exact=True without a literal kernel for this energy: the reference's torch operations, per transition
             if (spec is not None and spec.kind == _lib.ENERGY_GAUSSIAN and spec.dim is not None
@@ -210,6 +212,8 @@ class HamiltonianMonteCarlo(BaseSampler):
             dim = mean.shape[0]
         x = self._init_state(x, dim, n_samples, generator)
         route, spec = self._route(x, model_kwargs)
+        if route == "fused" and spec.kind == _lib.ENERGY_MLP3 and return_diagnostics:
+            route = "step"  # (the three-layer transition kernel keeps no records)
         if route == "fused":
             return self._sample_fused(x, spec, n_steps, thin, return_trajectory, return_diagnostics, generator)
         return self._sample_stepwise(
@@ -432,6 +436,14 @@ class HamiltonianMonteCarlo(BaseSampler):
             eps = eps_vals[t0]
             table = schedule_table(self, eps_vals, state.device)[t0 : t0 + n_mh]
         cptr = None if counts is None else counts.data_ptr() + 4 * t0
+        if spec_c.kind == _lib.ENERGY_MLP3:  # the three-hidden-layer MLP's own entry: no diagonal mass, no records (`_route`, `sample`)
+            assert records is None and m_diag is None and not self.exact
+            _lib.call(
+                "ebm_hmc_chain_mlp3_f32",
+                spec_c, _lib.ptr(state), n, dim, n_mh, self.n_leapfrog_steps, eps, _lib.ptr(table),
+                kind, m_scalar, thin, _lib.ptr(traj), None, cptr, None, None, seed, step, stream,
+            )
+            return
         if self.exact:  # the literal body (no in-kernel records: `_sample_fused` asks for none)
             assert records is None
             _lib.call(
