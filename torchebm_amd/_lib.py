@@ -23,7 +23,7 @@ ABI_VERSION = 9
 # energy kinds / enums: keep in sync with include/ebm_hip.h
 ENERGY_DOUBLE_WELL, ENERGY_HARMONIC, ENERGY_GAUSSIAN, ENERGY_GMM, ENERGY_MLP = 0, 1, 2, 3, 4
 ENERGY_ROSENBROCK, ENERGY_ACKLEY, ENERGY_RASTRIGIN = 5, 6, 7  # the landscapes (ABI 9): scalars only
-ENERGY_MLP3 = 8  # the three-hidden-layer MLP (include/ebm_hip_mlp3.h): taken by the entries of EXPORTS_MLP3, EXPORTS_MLP3_STREAM and EXPORTS_MLP3_HMC only
+ENERGY_MLP3 = 8  # the three-hidden-layer MLP (include/ebm_hip_mlp3.h): taken by the entries of EXPORTS_MLP3, EXPORTS_MLP3_STREAM, EXPORTS_MLP3_HMC and EXPORTS_MLP3_KINETIC only
 CHAIN_CLAMP, CHAIN_CONTRACTED = 1, 2  # the flag word `clamp_on` of the chain entries (ABI 8)
 NOISE_NORMAL, NOISE_UNIFORM, NOISE_RAW_U32 = 0, 1, 2
 MASS_NONE, MASS_SCALAR, MASS_DIAG = 0, 1, 2
@@ -119,6 +119,10 @@ EXPORTS_MLP3_STREAM = ("ebm_mlp3_image_bytes", "ebm_mlp3_image_f32", "ebm_energy
 #: the entry point declared in include/ebm_hip_mlp3_hmc.h, the companion header of that energy's HMC transition kernel at
 #: hidden width 64 (the same library, the same ABI version; tests/test_mlp3_hmc_gpu.py drives it)
 EXPORTS_MLP3_HMC = ("ebm_hmc_chain_mlp3_f32",)
+
+#: the entry point declared in include/ebm_hip_mlp3_kinetic.h, the companion header of that energy's underdamped-Langevin (BAOAB)
+#: kernel at hidden width 64 (the same library, the same ABI version; tests/test_mlp3_kinetic_gpu.py drives it)
+EXPORTS_MLP3_KINETIC = ("ebm_kinetic_chain_mlp3_f32",)
 
 #: number of calls made through each entry point in this process (tests use it to
 #: prove that a GPU test really went through the HIP library)
@@ -284,6 +288,7 @@ _PROTOTYPES = {
         C.c_int,
         [_ENERGY_P, _p, _i64, _i32, _i32, _i32, _f, _p, _i32, _d, _i32, _p, _p, _p, _p, _p, _u64, _u64, _p],
     ),
+    "ebm_kinetic_chain_mlp3_f32": (C.c_int, [_ENERGY_P, _p, _p, _i64, _i32, _i32, _d, _d, _d, _i32, _i32, _p, _p, _u64, _u64, _p]),
     "ebm_mlp3_image_bytes": (C.c_size_t, [_i32, _i32]),
     "ebm_mlp3_image_f32": (C.c_int, [_p, _i32, _i32, _p, _p]),
     "ebm_energy_grad_mlp3_stream_f32": (C.c_int, [_ENERGY_P, _p, _i64, _i32, _p, _p, _p]),

@@ -42,6 +42,7 @@ class FusedSpec:
     min_dim: int = 1  # narrowest state the energy is defined on (Rosenbrock: 2)
     langevin_only: bool = False  # fused for Euler-Maruyama Langevin chains, HMC and energy/gradient evaluation; no Heun / descent kernel
     hmc: bool = True  # ebm_hmc_chain_f32 takes this energy at this shape
+    kinetic: bool = False  # ebm_kinetic_chain_mlp3_f32 takes this energy at this shape (an MLP3Energy's spec only)
 
     def to_c(self) -> "_lib.EnergyDesc":
         d = _lib.EnergyDesc()

@@ -38,7 +38,12 @@ class MLP3Energy(BaseModel):
       configuration takes the per-step route;
     * at ``hidden == 64``, ``HamiltonianMonteCarlo.sample()`` is one launch of ``ebm_hmc_chain_mlp3_f32``
       (include/ebm_hip_mlp3_hmc.h, docs/design/mlp3_hmc.md) with no mass or a scalar one, ``exact`` off and no diagnostics;
-      ``thin``, ``return_trajectory`` and a scheduled step size stay in that launch.
+      ``thin``, ``return_trajectory`` and a scheduled step size stay in that launch;
+    * at ``hidden == 64``, ``UnderdampedLangevin.sample()`` with the sampler's opt-in ``fused_mlp = True`` is one launch of
+      ``ebm_kinetic_chain_mlp3_f32`` (include/ebm_hip_mlp3_kinetic.h, docs/design/mlp3_kinetic.md): BAOAB with no mass and a
+      constant step size; ``thin``, ``return_trajectory``, ``return_diagnostics``, ``velocity=`` and ``return_velocity`` stay in
+      that launch.  Without the opt-in, with a mass or a scheduled step size, and in ``sample_moments``, the sampler keeps its
+      eager route with the one-launch gradient.
 
     At ``hidden == 128`` and ``33 <= in_dim <= 128`` both go through the streamed bf16 kernel instead
     (``ebm_energy_grad_mlp3_stream_f32`` / ``ebm_langevin_chain_mlp3_stream_f32``, include/ebm_hip_mlp3_stream.h,
@@ -57,6 +62,9 @@ class MLP3Energy(BaseModel):
     STREAMED_MAX_DIM = {128: 128}
     #: hidden width -> widest input of the HMC transition kernel (csrc/mlp3_hmc.hip; docs/design/mlp3_hmc.md: every width measured)
     HMC_MAX_DIM = {64: 128}
+    #: hidden width -> widest input of the underdamped-Langevin kernel (csrc/mlp3_kinetic.hip; docs/design/mlp3_kinetic.md: every
+    #: width measured)
+    KINETIC_MAX_DIM = {64: 128}
     #: take the streamed bf16 kernel also where the exact-f32 kernel of FUSED_MAX_DIM serves (hidden 128, in_dim <= 32)
     streamed_bf16 = False
     ROWS_INDEPENDENT = True
@@ -128,7 +136,8 @@ class MLP3Energy(BaseModel):
                 _lib.call("ebm_mlp3_image_f32", packed.data_ptr(), int(self.hidden), int(self.in_dim), image.data_ptr(),
                           _lib.stream_handle(packed.device))
         return FusedSpec(_lib.ENERGY_MLP3, n_comp=int(self.hidden), dev0=packed, aux=image, langevin_only=True, dim=int(self.in_dim),
-                         hmc=image is None and self.in_dim <= self.HMC_MAX_DIM.get(self.hidden, 0))
+                         hmc=image is None and self.in_dim <= self.HMC_MAX_DIM.get(self.hidden, 0),
+                         kinetic=image is None and self.in_dim <= self.KINETIC_MAX_DIM.get(self.hidden, 0))
 
     def _hip_gradient(self, x: torch.Tensor, model_kwargs: Optional[dict]) -> Optional[torch.Tensor]:
         """``gradient()`` in one ``ebm_energy_grad_mlp3_f32`` launch (``ebm_energy_grad_mlp3_stream_f32`` when the spec carries an

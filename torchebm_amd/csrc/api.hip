@@ -9,6 +9,7 @@
 #include "../../include/ebm_hip_mass_mlp.h"  // the two massed MLP walks' declarations (a companion of ebm_hip.h)
 #include "ghmc_adapt_launch.h"               // the adapting generalized-HMC entry (its companion header: ebm_hip_adapt.h)
 #include "ghmc_adapt_mass_launch.h"          // ... with a mass (its companion header: ebm_hip_adapt_mass.h)
+#include "mlp3_kinetic_launch.h"             // underdamped Langevin on the three-hidden-layer MLP (its companion header: ebm_hip_mlp3_kinetic.h)
 
 namespace ebm {
 
@@ -704,6 +705,31 @@ int ebm_kinetic_mlp_chain_mass_f32(const ebm_energy_t* energy, float* x, float* 
   const ChainMass mass{mass_kind, mass_scalar, mass_diag};
   return kinetic_chain_impl("ebm_kinetic_mlp_chain_mass_f32", true, energy, x, v, n_chains, dim, k_steps, h, gamma, temperature,
                             draw_v0, thin, traj, noise, seed, offset, stream, &mass);
+}
+
+// ... on the three-hidden-layer MLP energy at hidden width 64 (include/ebm_hip_mlp3_kinetic.h): the same parameter list and the same
+// constants; the refusals in the order that header states, all of them before the early return
+int ebm_kinetic_chain_mlp3_f32(const ebm_energy_t* energy, float* x, float* v, int64_t n_chains, int32_t dim, int32_t k_steps,
+                               double h, double gamma, double temperature, int32_t draw_v0, int32_t thin, float* traj,
+                               const float* noise, uint64_t seed, uint64_t offset, void* stream) {
+  const char* who = "ebm_kinetic_chain_mlp3_f32";
+  if (!energy) return fail(EBM_EINVAL, "%s: energy descriptor is NULL", who);
+  if (energy->kind != EBM_ENERGY_MLP3) return fail(EBM_EKIND, "%s: this entry takes EBM_ENERGY_MLP3 only (got kind %d)", who, energy->kind);
+  if (!energy->dev0) return fail(EBM_EINVAL, "%s: the energy needs the packed parameter pointer", who);
+  if (!x) return fail(EBM_EINVAL, "%s: state pointer is NULL", who);
+  if (!v) return fail(EBM_EINVAL, "%s: velocity pointer is NULL", who);
+  if (n_chains < 0 || k_steps < 1 || thin < 1)
+    return fail(EBM_EINVAL, "%s: n_chains=%lld k_steps=%d thin=%d", who, (long long)n_chains, k_steps, thin);
+  if (energy->n_comp != 64 || dim < 1 || dim > 128)
+    return fail(EBM_EDIM, "%s: hidden width %d, dim %d (the kernel takes hidden width 64 with dim 1 .. 128)", who, energy->n_comp, dim);
+  if (!(h > 0.0) || !(gamma > 0.0) || !(temperature > 0.0) || !std::isfinite(h) || !std::isfinite(gamma) || !std::isfinite(temperature))
+    return fail(EBM_EINVAL, "%s: h=%g gamma=%g temperature=%g (all must be positive and finite)", who, h, gamma, temperature);
+  if (!aligned16(x) || !aligned16(v) || (traj && !aligned16(traj)) || (noise && !aligned16(noise)))
+    return fail(EBM_EINVAL, "%s: x / v / traj / noise must be 16-byte aligned", who);
+  if (n_chains == 0) return 0;
+  return kinetic_mlp3_chain_launch(kinetic_request(energy, x, v, n_chains, dim, k_steps, h, gamma, temperature, draw_v0, thin, traj,
+                                                   noise, seed, offset),
+                                   (hipStream_t)stream);
 }
 
 // The request of both generalized-HMC entries: the constants of the refresh over one trajectory's time eps L, formed in double,

@@ -21,6 +21,9 @@ Two execution routes, chosen once per ``sample()`` call (``_route``):
            (docs/design/kinetic_mlp.md), the evaluation on the matrix cores inside the step loop.  Its gradients are the kernel's
            (fp32-accurate, not autograd's rounding) and its draws the Philox field's, so the default stays ``eager`` for the MLP
            and a call made without the opt-in is bit for bit what it was.
+``fused_mlp3``  the same opt-in on an ``MLP3Energy`` of hidden width 64 with ``dim == in_dim <= 128``, unit mass: ONE launch of
+           ``ebm_kinetic_chain_mlp3_f32`` (docs/design/mlp3_kinetic.md), the same parameter list and Philox steps as ``fused_mlp``.
+           With a mass, a scheduled step size or hidden width 128, and inside ``sample_moments``, this energy stays ``eager``.
 ``eager``  everything else (CPU, any other ``BaseModel``, a scheduler on ``step_size``, wider rows, ``model_kwargs``): the same
            recurrence in torch ops around ``model.gradient``, drawing ``randn(n, dim)`` for the start velocities and once per
            step.
@@ -45,6 +48,7 @@ import torch
 
 from .. import _lib, _rng
 from ..core.energies import BaseModel, FusedSpec, fused_spec_for
+from ..core.mlp3 import MLP3Energy
 from ..core.sampler_base import BaseSampler
 from ..core.schedules import BaseScheduler
 from ..integrators.symplectic import _mass_args
@@ -86,6 +90,7 @@ class UnderdampedLangevin(BaseSampler):
     #: is ONE launch of ``ebm_kinetic_mlp_chain_mass_f32`` (docs/design/mass_mlp.md).  Off by default: with ``fused_mlp`` alone a
     #: massed sampler on an ``MLPEnergy`` keeps the eager route and its bits.
     fused_mlp_mass = False
+    _in_sample_moments = False  # set while ``sample_moments`` runs
 
     def __init__(
         self,
@@ -117,9 +122,14 @@ class UnderdampedLangevin(BaseSampler):
             return "eager", None
         if self.use_mixed_precision and self.autocast_available:
             return "eager", None
-        spec = fused_spec_for(self.model, x, None)
+        # an MLP3Energy forms its spec only for a caller that asks for its kind: this one does under the opt-in, with unit mass and
+        # outside sample_moments (whose step-by-step recurrence calls sample() once per step and keeps the eager steps' bits)
+        mlp3 = self.fused_mlp and self.mass is None and not self._in_sample_moments and isinstance(self.model, MLP3Energy)
+        spec = fused_spec_for(self.model, x, None, mlp3=mlp3)
         if spec is None or x.shape[1] > FUSED_MAX_DIM:
             return "eager", None
+        if spec.kind == _lib.ENERGY_MLP3:
+            return ("fused_mlp3", spec) if spec.kinetic else ("eager", None)
         if spec.kind == _lib.ENERGY_MLP:
             fits = self.fused_mlp and fused_mlp_walk_fits(spec.n_comp, getattr(self.model, "in_dim", None), x.shape[1])
             if self.mass is not None:  # (a second opt-in: with fused_mlp alone a massed MLP sampler stays eager)
@@ -186,6 +196,9 @@ class UnderdampedLangevin(BaseSampler):
         elif route == "fused_mlp":
             state, v, traj, diag = self._sample_fused(x, velocity, spec, n_steps, thin, return_trajectory, return_diagnostics, generator,
                                                       entry="ebm_kinetic_mlp_chain_f32")
+        elif route == "fused_mlp3":
+            state, v, traj, diag = self._sample_fused(x, velocity, spec, n_steps, thin, return_trajectory, return_diagnostics, generator,
+                                                      entry="ebm_kinetic_chain_mlp3_f32")
         elif route == "fused_mlp_mass":
             state, v, traj, diag = self._sample_fused(x, velocity, spec, n_steps, thin, return_trajectory, return_diagnostics, generator,
                                                       entry="ebm_kinetic_mlp_chain_mass_f32")
@@ -230,7 +243,11 @@ class UnderdampedLangevin(BaseSampler):
         """
         from .kinetic_moments import sample_moments
 
-        return sample_moments(self, False, x, dim, n_steps, n_samples, burn_in, energy, velocity, return_velocity, generator)
+        self._in_sample_moments = True  # (read by `_route`: an MLP3Energy keeps the eager steps here)
+        try:
+            return sample_moments(self, False, x, dim, n_steps, n_samples, burn_in, energy, velocity, return_velocity, generator)
+        finally:
+            self._in_sample_moments = False
 
     # ---------------------------------------------------------------------------------
     # route: torch ops
@@ -306,7 +323,7 @@ class UnderdampedLangevin(BaseSampler):
         if want_diag:
             diag = new_outputs(state, state.shape, n_kept, False, True)[1]
             if n > 0 and n_kept > 0:
-                if spec.kind == _lib.ENERGY_MLP:  # the kept positions' statistics in torch ops, their energy the model's
+                if spec.kind in (_lib.ENERGY_MLP, _lib.ENERGY_MLP3):  # the kept positions' statistics in torch ops, their energy the model's
                     for keep in range(n_kept):
                         record_kept(traj[:, keep], keep, None, diag, lambda x_: self._model_energy(x_, {}))
                 else:
